@@ -41,6 +41,12 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 CORR = dict(B=8, C=256, H=48, W=64, pad=20, k=1, md=20, s1=1, s2=2)
 IMG = dict(B=8, C=3, H=384, W=512)
+# ranks of a FN2_BENCH_SHARE_GPU=1 dry run, all on cuda:0: with the launching process (a test runner that holds the GPU too)
+# no more than six processes have one GPU open at the same time
+MAX_SHARED_RANKS = 4
+# --dump-outputs: outputs above this many elements are written as a seeded sample (8 outputs x 4 MiB of fp32 at most)
+DUMP_MAX_ELEMS = 1 << 20
+DUMP_SEED = 0
 
 
 def corr_fwd_bytes(B=CORR["B"]):
@@ -138,6 +144,30 @@ class HotPath:
             self.gimg.zero_()   # the reference wrapper zero-fills grad_input1 every call (resample2d.py:31)
             self.m_res.backward(self.img, self.flow, self.gwarp, self.gimg, self.gflow, 1, True)
         timed("resample_bwd", res_bwd)
+
+    def outputs(self):
+        """What a caller of the step receives, by the reference's names: each module's forward output and backward gradients."""
+        return {"correlation_output": self.out, "correlation_grad_input1": self.g1, "correlation_grad_input2": self.g2,
+                "resample2d_output": self.warped, "channelnorm_output": self.norm, "channelnorm_grad_input": self.gdiff,
+                "resample2d_grad_input1": self.gimg, "resample2d_grad_input2": self.gflow}
+
+    def dump_outputs(self, dirname):
+        """--dump-outputs: the step's outputs as `dirname`/<name>.npy in their own dtype (fp32 here).  An output of more than
+        DUMP_MAX_ELEMS elements is written as a fixed sample: the flat elements at sorted positions drawn by a generator seeded
+        with DUMP_SEED, the same positions in every run.  Returns what was written, for the JSON line."""
+        import numpy as np
+        os.makedirs(dirname, exist_ok=True)
+        written = {}
+        for name, t in self.outputs().items():
+            a = t.detach()
+            entry = {"shape": list(a.shape), "dtype": str(a.dtype).replace("torch.", "")}
+            if a.numel() > DUMP_MAX_ELEMS:
+                pos = np.sort(np.random.default_rng(DUMP_SEED).choice(a.numel(), DUMP_MAX_ELEMS, replace=False))
+                a = a.reshape(-1)[torch.from_numpy(pos).to(a.device)]
+                entry["sample"] = {"elements": DUMP_MAX_ELEMS, "seed": DUMP_SEED}
+            np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+            written[name] = entry
+        return {"dir": os.path.abspath(dirname), "arrays": written}
 
 
     def module_steps(self, steps):
@@ -588,6 +618,8 @@ def launch_plan(gpus, device_count, share):
     if device_count < gpus and not share:
         return None, (f"--gpus {gpus} but only {device_count} GPU(s) visible (FN2_BENCH_SHARE_GPU=1 runs the N-rank control "
                       "flow on one GPU over gloo as a dry run)")
+    if share and gpus > MAX_SHARED_RANKS:
+        return None, (f"--gpus {gpus} as a shared-GPU dry run: at most {MAX_SHARED_RANKS} ranks may open one GPU at the same time")
     return [{"RANK": str(r), "LOCAL_RANK": str(r), "WORLD_SIZE": str(gpus), "MASTER_ADDR": "127.0.0.1",
              "LOCAL_WORLD_SIZE": str(gpus)} for r in range(gpus)], None
 
@@ -664,7 +696,12 @@ def main():
     ap.add_argument("--model-steps", type=int, default=20)
     ap.add_argument("--model-warmup", type=int, default=5)
     ap.add_argument("--model-timeout", type=float, default=240.0, help="seconds after which the FlowNet2C pass is abandoned")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (rank 0's; large outputs as a "
+                         "fixed seeded sample, 32 MiB in all): the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import dist_utils
     assert torch.cuda.is_available(), "bench.py needs a GPU: the HIP kernels are the only implementation"
@@ -783,6 +820,8 @@ def main():
     elapsed = time.perf_counter() - t0
     own_elapsed = elapsed
     elapsed = dist_utils.max_over_ranks(elapsed, device=dev)   # the step time is the slowest rank's
+    # the timed path's results, before anything after the timed region launches the same kernels into the same buffers again
+    dumped = hp.dump_outputs(args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # per-rank consistency check: every rank's own time for its K steps and a checksum of its results
     chk = float(hp.out.double().sum().item() + hp.g1.double().sum().item() + hp.norm.double().sum().item())
     # two probes of THIS rank's GPU, so that an N-GPU line explains itself (the step time is the slowest rank's): the graded kernel
@@ -1038,6 +1077,8 @@ def main():
         assert len(per_rank) == world and all(r["finite"] for r in per_rank), per_rank
         if share:
             line["dry_run_shared_gpu"] = True
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             line["gpu_over_cpu"] = round(line["value"] / line["cpu_baseline"]["value"], 1)

@@ -14,6 +14,15 @@ matplotlib.use("Agg")
 from utils import flow_utils as ref  # noqa: E402
 
 
+def flow2img_cases():
+    """The flows of tests/test_flo.py::test_flow2img_against_the_live_reference, drawn as it draws them."""
+    rng = np.random.default_rng(77)
+    for shape, scale in (((17, 23, 2), 1.0), ((8, 8, 2), 1e-6), ((30, 5, 2), 400.0)):
+        flow = (rng.standard_normal(shape) * scale).astype(np.float32)
+        flow[0, 0] = (5e7, 0.0)
+        yield flow
+
+
 def main():
     rng = np.random.default_rng(20260923)
     cases = {}
@@ -30,6 +39,12 @@ def main():
             np.save(os.path.join(OUT, "flowvis_%s.npy" % k), ref.flow2img(np.array(v, copy=True)))    # the reference edits its argument
     np.save(os.path.join(OUT, "flowvis_wheel.npy"), ref.make_color_wheel())
     np.savez(os.path.join(OUT, "flowvis_inputs.npz"), **cases)
+    # tests/test_flo.py::test_flow2img_against_the_live_reference: its seeded flows (regenerated there) and the reference's images
+    live = {}
+    for i, flow in enumerate(flow2img_cases()):
+        with np.errstate(all="ignore"):
+            live["case%d" % i] = ref.flow2img(flow.copy())
+    np.savez(os.path.join(OUT, "flowvis_seeded_cases.npz"), **live)
     print("wrote", sorted(f for f in os.listdir(OUT) if f.startswith("flowvis_")))
 
 

@@ -23,6 +23,10 @@ def test_launch_plan():
     assert plan is None and "only 1 GPU" in err                         # refuses instead of oversubscribing silently
     plan, err = bench.launch_plan(2, 1, True)                           # FN2_BENCH_SHARE_GPU=1: labelled dry run
     assert err is None and len(plan) == 2
+    plan, err = bench.launch_plan(bench.MAX_SHARED_RANKS, 1, True)
+    assert err is None and len(plan) == bench.MAX_SHARED_RANKS
+    plan, err = bench.launch_plan(8, 1, True)                           # no more ranks on one shared GPU than it may hold
+    assert plan is None and "at most" in err
     assert bench.launch_plan(0, 8, False)[0] is None
 
 
@@ -104,26 +108,29 @@ def test_bench_gpus_2_self_launch():
 @pytest.mark.gpu
 def test_bench_gpus_8_line_explains_itself():
     """the 8-rank line before an 8-GPU node shows up -- over RCCL where the box has eight GPUs, else the labelled
-    shared-GPU dry run.  Eight `per_rank` entries, each with its own step time, pairs/s, the graded kernel's warm time and a copy
-    rate of ITS GPU, and the fastest-over-slowest ratio that caps the run's scaling efficiency."""
+    shared-GPU dry run with as many ranks as one GPU may hold (bench.MAX_SHARED_RANKS).  One `per_rank` entry per rank, each with its
+    own step time, pairs/s, the graded kernel's warm time and a copy rate of ITS GPU, and the fastest-over-slowest ratio that caps the
+    run's scaling efficiency."""
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     share = torch.cuda.device_count() < 8
+    n = bench.MAX_SHARED_RANKS if share else 8
     if share:
         env["FN2_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--model", "off"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 8 and line["scaling"] == "weak" and line["value"] > 0
-    assert len(line["per_rank"]) == 8
+    assert line["n_gpus"] == n and line["scaling"] == "weak" and line["value"] > 0
+    assert line.get("dry_run_shared_gpu", False) == share
+    assert len(line["per_rank"]) == n
     for p in line["per_rank"]:
         assert p["finite"] and p["ms_per_step"] > 0 and p["image_pairs_per_s"] > 0 and p["corr_fwd_us_warm"] > 0 and p["copy_GBps_torch"] > 0
         # round 6: where the rank ran -- the GPU's slot and the host cores it pinned itself to
         assert {"pci_bus_id", "numa_node", "xgmi_hive_id", "hip_visible_devices", "cpu_cores", "pid"} <= set(p)
-    assert len({p["cpu_cores"] for p in line["per_rank"]}) == 8                 # eight disjoint core sets
+    assert len({p["cpu_cores"] for p in line["per_rank"]}) == n                 # one core set per rank
     assert line["launch"].startswith("hipGraph") and "placement_autotune" in line
     slowest = max(p["ms_per_step"] for p in line["per_rank"])
     assert abs(line["ms_per_step"] - slowest) <= 0.25 * slowest + 0.05       # the step time is the slowest rank's (barriers aside)

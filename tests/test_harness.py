@@ -1,6 +1,7 @@
 """the FlowNet2C harness -- network definition (state-dict compatible with the reference's class),
 bucketed gradient all-reduce (world_size-2 gloo on CPU), one training step and inference on the GPU."""
 import importlib
+import json
 import os
 import socket
 import sys
@@ -12,7 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
-from conftest import PKG, ROOT
+from conftest import GOLDEN, PKG, ROOT
 
 REF = "/root/reference"
 
@@ -26,51 +27,53 @@ def test_flownet2c_parameter_table():
     assert sd["deconv2.0.weight"].shape == (386, 64, 4, 4) and sd["upsampled_flow3_to_2.bias"].shape == (2,)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "networks")), reason="reference checkout not present")
-def test_flownet2c_state_dict_matches_reference_class():
-    """Key names and shapes equal those of the reference's models.FlowNet2C, so its checkpoints load unchanged."""
-    from harness.flownet2c import FlowNet2C
-    ours = {k: tuple(v.shape) for k, v in FlowNet2C().state_dict().items()}
+def _reference_state_dict_shapes(name):
+    """{key: shape} of the reference's models.<name>: the live class where the reference checkout exists (and then the committed
+    fixture must equal it), else tests/golden/refmodels_state_dict_shapes.json, which tests/golden/make_golden_state_dicts.py wrote
+    from that class."""
+    with open(os.path.join(GOLDEN, "refmodels_state_dict_shapes.json")) as f:
+        fixture = {k: tuple(v) for k, v in json.load(f)[name].items()}
+    if not os.path.isdir(os.path.join(REF, "networks")):
+        return fixture
     saved_path, saved_mods = list(sys.path), dict(sys.modules)
     for k in [k for k in sys.modules if k == "networks" or k.startswith("networks.") or k == "models"]:
         del sys.modules[k]
     sys.path.insert(0, REF)
     try:
         ref_models = importlib.import_module("models")
-        ref = ref_models.FlowNet2C(SimpleNamespace(rgb_max=255.0, fp16=False))
-        theirs = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-        assert ours == theirs
-        net = FlowNet2C()
-        net.load_state_dict(ref.state_dict())                               # strict
+        live = {k: tuple(v.shape) for k, v in getattr(ref_models, name)(SimpleNamespace(rgb_max=255.0, fp16=False)).state_dict().items()}
     finally:
         sys.path[:] = saved_path
         for k in [k for k in sys.modules if k not in saved_mods]:
             del sys.modules[k]
         sys.modules.update(saved_mods)
+    assert list(live.items()) == list(fixture.items())
+    return live
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "networks")), reason="reference checkout not present")
+def _strict_load(net, shapes):
+    """load_state_dict(strict) of a state dict with exactly these keys and shapes (what loading the reference's checkpoint checks)."""
+    net.load_state_dict({k: torch.zeros(s) for k, s in shapes.items()})
+
+
+def test_flownet2c_state_dict_matches_reference_class():
+    """Key names and shapes equal those of the reference's models.FlowNet2C, so its checkpoints load unchanged."""
+    from harness.flownet2c import FlowNet2C
+    ours = {k: tuple(v.shape) for k, v in FlowNet2C().state_dict().items()}
+    theirs = _reference_state_dict_shapes("FlowNet2C")
+    assert ours == theirs
+    _strict_load(FlowNet2C(), theirs)
+
+
 def test_flownet2_state_dict_matches_reference_class():
     """The full stack (FlowNetC + 2 x FlowNetS + FlowNetSD + FlowNetFusion): same keys and shapes as models.FlowNet2."""
     from harness.flownet2 import FlowNet2
     ours = FlowNet2()
     assert sum(p.numel() for p in ours.parameters()) == 162_518_834          # models.py:27
     mine = {k: tuple(v.shape) for k, v in ours.state_dict().items()}
-    saved_path, saved_mods = list(sys.path), dict(sys.modules)
-    for k in [k for k in sys.modules if k == "networks" or k.startswith("networks.") or k == "models"]:
-        del sys.modules[k]
-    sys.path.insert(0, REF)
-    try:
-        ref_models = importlib.import_module("models")
-        ref = ref_models.FlowNet2(SimpleNamespace(rgb_max=255.0, fp16=False))
-        theirs = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-        assert mine == theirs
-        ours.load_state_dict(ref.state_dict())
-    finally:
-        sys.path[:] = saved_path
-        for k in [k for k in sys.modules if k not in saved_mods]:
-            del sys.modules[k]
-        sys.modules.update(saved_mods)
+    theirs = _reference_state_dict_shapes("FlowNet2")
+    assert mine == theirs
+    _strict_load(ours, theirs)
 
 
 # ---------------------------------------------------------------- bucketed all-reduce, world_size 2 on gloo

@@ -1,6 +1,6 @@
 """Restated oracle vs the reference's kernels executed live under the CPU SIMT shim
-(oracle/_ref/libfn2_ref.so).  Skipped where the .so has not been built; it is built in the dev
-container (where /root/reference exists) and travels to the GPU box with the snapshot."""
+(oracle/_ref/libfn2_ref.so, built where the reference checkout exists); elsewhere vs their answers to
+these same calls, recorded in tests/golden/oracle_vs_ref_calls.npz (tests/golden/make_golden_oracle_vs_ref.py)."""
 import numpy as np
 import pytest
 
