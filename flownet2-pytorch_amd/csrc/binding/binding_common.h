@@ -17,7 +17,8 @@ inline int dtype_of(const at::Tensor &t, const char *op)
     case at::kFloat: return FN2_F32;
     case at::kHalf: return FN2_F16;
     case at::kDouble: return FN2_F64;
-    default: TORCH_CHECK(false, op, ": unsupported dtype ", t.scalar_type(), " (float, half or double expected)");
+    case at::kBFloat16: return FN2_BF16;
+    default: TORCH_CHECK(false, op, ": unsupported dtype ", t.scalar_type(), " (float, half, double or bfloat16 expected)");
     }
     return -1;
 }

@@ -63,24 +63,24 @@ int correlation_forward_fused_hip(at::Tensor &input1, at::Tensor &input2, at::Te
     return 1;
 }
 
-// Half tensors on maps wider than 64 px (Sintel-size conv3): there is no tiled half kernel for that corner (the narrow one holds
-// whole rows of <= 64 px), and the general kernel takes milliseconds.  The fp32 column-window kernel on widened copies is
-// ~25x faster and a superset numerically (exact products of the half operands, fp32 sums; the reference sums in half,
-// correlation_cuda_kernel.cu:229): widen, run, narrow -- three elementwise passes around a 0.3 ms kernel instead of 9 ms.
-// Shared by backward and backward_fused.  `go`: the contiguous half gradient.  false = not this corner (or a shape the
-// fp32 launchers decline): the caller's half path takes it.
+// Half and bfloat16 tensors on maps wider than 64 px (Sintel-size conv3): there is no tiled 16-bit backward kernel for that corner
+// (the narrow one holds whole rows of <= 64 px), and the general kernel takes milliseconds.  The fp32 column-window kernel on
+// widened copies is ~25x faster and a superset numerically (exact products of the 16-bit operands, fp32 sums; the reference sums
+// in half, correlation_cuda_kernel.cu:229): widen, run, narrow once -- three elementwise passes around a 0.3 ms kernel instead of
+// 9 ms.  Shared by backward and backward_fused.  `go`: the contiguous gradient in the inputs' dtype.  false = not this
+// corner (or a shape the fp32 launchers decline): the caller's 16-bit path takes it.
 // The shapes that corner covers (pure predicate: callers test it BEFORE preparing operands for it).
-static bool half_wide_applies(int dt, int C, int H, int W, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2)
+static bool wide16_applies(int dt, int C, int H, int W, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2)
 {
-    return dt == FN2_F16 && W > 64 && kernel_size == 1 && stride1 == 1 && stride2 == 2 && pad_size == max_displacement &&
+    return (dt == FN2_F16 || dt == FN2_BF16) && W > 64 && kernel_size == 1 && stride1 == 1 && stride2 == 2 && pad_size == max_displacement &&
            max_displacement == 20 && C % 64 == 0 && H % 2 == 0 && W % 8 == 0;
 }
 
-static bool half_wide_backward(const at::Tensor &a, const at::Tensor &b, const at::Tensor &go, at::Tensor &gradInput1, at::Tensor &gradInput2,
+static bool wide16_backward(const at::Tensor &a, const at::Tensor &b, const at::Tensor &go, at::Tensor &gradInput1, at::Tensor &gradInput2,
                                int dt, int B, int C, int H, int W, int pad_size, int kernel_size, int max_displacement, int stride1,
                                int stride2)
 {
-    if (!half_wide_applies(dt, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
+    if (!wide16_applies(dt, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
         return false;
     at::Tensor a32 = a.to(at::kFloat), b32 = b.to(at::kFloat), go32 = go.to(at::kFloat);
     at::Tensor g1 = at::empty_like(a32), g2 = at::empty_like(b32);
@@ -119,7 +119,7 @@ int correlation_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor 
     gradInput1.resize_({B, C, H, W});        // correlation_cuda.cc:108-109; fully written, no fill_(0)
     gradInput2.resize_({B, C, H, W});
     TORCH_CHECK(gradInput1.is_contiguous() && gradInput2.is_contiguous(), op, ": gradInputs must be contiguous");
-    if (half_wide_backward(a, b, go, gradInput1, gradInput2, dt, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
+    if (wide16_backward(a, b, go, gradInput1, gradInput2, dt, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
         return 1;
     check_rc(fn2_correlation_backward(a.data_ptr(), b.data_ptr(), go.data_ptr(), gradInput1.data_ptr(),
                                       gradInput2.data_ptr(), dt, B, C, H, W, pad_size, kernel_size, max_displacement,
@@ -161,12 +161,13 @@ int correlation_backward_fused_hip(at::Tensor &input1, at::Tensor &input2, at::T
     // the activation's derivative is read off the SIGN of the stored output: only an increasing activation keeps it
     // (fn2_correlation_backward_fused enforces the same; checked here so that no branch below can run without it)
     TORCH_CHECK(negative_slope > 0, op, ": negative_slope must be > 0, got ", negative_slope);
-    if (half_wide_applies(dt, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
-        // the masked gradient as autograd's leaky_relu_backward forms it for half tensors (fp32 product, rounded to half once), then
-        // the same widened path as `backward`: fused and unfused training give the same gradients on Sintel-size maps too
+    if (wide16_applies(dt, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
+        // the masked gradient as autograd's leaky_relu_backward forms it for 16-bit tensors (fp32 product, rounded to the inputs'
+        // type once), then the same widened path as `backward`: fused and unfused training give the same gradients on Sintel-size
+        // maps too
         at::Tensor outs = buffer.narrow(1, channel_offset, nOut), gs = gb.narrow(1, channel_offset, nOut).to(at::kFloat);
-        at::Tensor masked = at::where(outs > 0, gs, gs * (float)negative_slope).to(at::kHalf).contiguous();
-        if (half_wide_backward(a, b, masked, gradInput1, gradInput2, dt, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
+        at::Tensor masked = at::where(outs > 0, gs, gs * (float)negative_slope).to(input1.scalar_type()).contiguous();
+        if (wide16_backward(a, b, masked, gradInput1, gradInput2, dt, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2))
             return 1;
     }
     const size_t wsb = fn2_correlation_backward_fused_workspace_bytes(dt, B, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);

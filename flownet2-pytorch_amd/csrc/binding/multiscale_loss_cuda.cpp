@@ -41,6 +41,18 @@ at::Tensor primed_workspace(const at::Tensor &like, void *stream, size_t bytes)
     return ws;
 }
 
+// A prediction as the float32 kernel reads it: float32 as it is; half and bfloat16 (mixed-precision training) widened, exactly.
+// The loss and EPE are then float32 sums and the gradients are formed in float32 and rounded once to the prediction's dtype.
+at::Tensor widened_prediction(const at::Tensor &target, const at::Tensor &o, const char *op)
+{
+    check_gpu(o, op, "a prediction");
+    TORCH_CHECK(o.device() == target.device(), op, ": a prediction is on ", o.device(), ", expected ", target.device());
+    const auto st = o.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, op, ": predictions must be float32, float16 or bfloat16, got ",
+                st);
+    return st == at::kFloat ? o.contiguous() : o.to(at::kFloat).contiguous();
+}
+
 struct MultiScaleOp : public torch::autograd::Function<MultiScaleOp> {
     // returns {loss, epe}; epe is not differentiable
     // want_grads: decided by the caller of apply() (grad mode on and a prediction requires a gradient) -- inside forward grad mode is
@@ -60,15 +72,16 @@ struct MultiScaleOp : public torch::autograd::Function<MultiScaleOp> {
         const int B = target.size(0), H = target.size(2), W = target.size(3);
         const bool any_grad = want_grads;
         std::vector<at::Tensor> outs(n), grads;
+        std::vector<int64_t> dtypes(n);
         const float *optr[6] = {nullptr};
         float *gptr[6] = {nullptr};
         float w[6] = {0};
         for (int i = 0; i < n; ++i) {
             const int64_t k = start_scale << i;
-            check_same(target, outputs[i], op, "a prediction");
+            outs[i] = widened_prediction(target, outputs[i], op);
+            dtypes[i] = (int64_t)outputs[i].scalar_type();
             TORCH_CHECK(outputs[i].dim() == 4 && outputs[i].size(0) == B && outputs[i].size(1) == 2 && outputs[i].size(2) == H / k && outputs[i].size(3) == W / k,
                         op, ": prediction ", i, " has shape ", outputs[i].sizes(), ", expected [", B, ", 2, ", H / k, ", ", W / k, "]");
-            outs[i] = outputs[i].contiguous();
             optr[i] = outs[i].data_ptr<float>();
             w[i] = (float)weights[i];
         }
@@ -89,6 +102,7 @@ struct MultiScaleOp : public torch::autograd::Function<MultiScaleOp> {
                                            (int)start_scale, n, (float)div_flow, ws.data_ptr(), wsb, 1, stream), op);
         if (any_grad) ctx->save_for_backward(grads);
         ctx->saved_data["n"] = (int64_t)n;
+        ctx->saved_data["dtypes"] = dtypes;
         at::Tensor loss = res.select(0, 0), epe = res.select(0, 1);
         ctx->mark_non_differentiable({epe});
         return {loss, epe};
@@ -117,6 +131,9 @@ struct MultiScaleOp : public torch::autograd::Function<MultiScaleOp> {
             numel[i] = saved[i].numel();
         }
         check_rc(fn2_multiscale_scale_grads(in, out, numel, n, g.data_ptr<float>(), current_stream(g)), op);
+        const auto dtypes = ctx->saved_data["dtypes"].toIntVector();
+        for (int i = 0; i < n; ++i)   // a gradient comes back in its prediction's dtype (one rounding for half / bfloat16)
+            if (result[1 + i].defined() && dtypes[i] != (int64_t)at::kFloat) result[1 + i] = result[1 + i].to((at::ScalarType)dtypes[i]);
         return result;
     }
 };
@@ -142,8 +159,7 @@ at::Tensor multiscale_sums(const at::Tensor &target, std::vector<at::Tensor> out
     std::vector<at::Tensor> outs(n);
     const float *optr[6] = {nullptr};
     for (int i = 0; i < n; ++i) {
-        check_same(t, outputs[i], op, "a prediction");
-        outs[i] = outputs[i].contiguous();
+        outs[i] = widened_prediction(t, outputs[i], op);
         optr[i] = outs[i].data_ptr<float>();
     }
     const int B = t.size(0), H = t.size(2), W = t.size(3);

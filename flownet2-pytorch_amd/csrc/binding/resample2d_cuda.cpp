@@ -1,8 +1,19 @@
 // resample2d_cuda.cpp -- pybind module `resample2d_cuda` (drop-in for the reference's module,
-// resample2d_cuda.cc:6-31).  float32 only, as in the reference (resample2d_kernel.cu:221-230).
+// resample2d_cuda.cc:6-31).  float32, as in the reference (resample2d_kernel.cu:221-230); forward / backward also take bfloat16
+// tensors (mixed-precision training) by widening them to float32 around the float32 kernels -- see widen_bf16 below.
 #include "binding_common.h"
 
 using namespace fn2b;
+
+// The float32 tensors the kernels expect: float32 passes through, bfloat16 is widened (exact) once; anything else is refused with
+// the reference's message.  The caller rounds each result to bfloat16 once (copy_ into the bfloat16 tensor).
+static bool widen_bf16(const at::Tensor &t, const char *op)
+{
+    const bool bf = t.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(t.scalar_type() == at::kFloat || bf, op, ": float32 tensors expected (bfloat16 is widened to float32), got ",
+                t.scalar_type());
+    return bf;
+}
 
 static void strides4(const at::Tensor &t, int64_t s[4])
 {
@@ -17,7 +28,7 @@ int resample2d_forward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &o
     check_gpu(input1, op, "input1");
     check_same(input1, input2, op, "input2");
     check_same(input1, output, op, "output");
-    TORCH_CHECK(input1.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", input1.scalar_type());
+    const bool bf = widen_bf16(input1, op);
     TORCH_CHECK(input1.dim() == 4 && input2.dim() == 4 && output.dim() == 4, op, ": tensors must be 4-D");
     TORCH_CHECK(input2.size(1) == 2, op, ": input2 (flow) must have 2 channels, got ", input2.size(1));
     const int B = output.size(0), C = output.size(1), H = output.size(2), W = output.size(3);
@@ -27,12 +38,15 @@ int resample2d_forward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &o
                 output.sizes());
     TORCH_CHECK(output.is_contiguous(), op, ": output must be contiguous");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor flow = input2.contiguous();
+    at::Tensor img = bf ? input1.to(at::kFloat) : input1;
+    at::Tensor flow = bf ? input2.to(at::kFloat).contiguous() : input2.contiguous();
+    at::Tensor out = bf ? at::empty(output.sizes(), output.options().dtype(at::kFloat)) : output;
     int64_t is[4];
-    strides4(input1, is); // honoured by the kernel, like the reference's DIM3_INDEX
-    check_rc(fn2_resample2d_forward(input1.data_ptr<float>(), is, flow.data_ptr<float>(), output.data_ptr<float>(), B,
-                                    C, (int)input1.size(2), (int)input1.size(3), H, W, kernel_size, bilinear ? 1 : 0,
+    strides4(img, is); // honoured by the kernel, like the reference's DIM3_INDEX
+    check_rc(fn2_resample2d_forward(img.data_ptr<float>(), is, flow.data_ptr<float>(), out.data_ptr<float>(), B,
+                                    C, (int)img.size(2), (int)img.size(3), H, W, kernel_size, bilinear ? 1 : 0,
                                     current_stream(input1)), op);
+    if (bf) output.copy_(out);
     return 1;
 }
 
@@ -47,7 +61,7 @@ int resample2d_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &
     check_same(input1, gradOutput, op, "gradOutput");
     check_same(input1, gradInput1, op, "gradInput1");
     check_same(input1, gradInput2, op, "gradInput2");
-    TORCH_CHECK(input1.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", input1.scalar_type());
+    const bool bf = widen_bf16(input1, op);
     TORCH_CHECK(input1.dim() == 4 && input2.dim() == 4 && gradOutput.dim() == 4, op, ": tensors must be 4-D");
     const int B = gradOutput.size(0), C = gradOutput.size(1), H = gradOutput.size(2), W = gradOutput.size(3);
     TORCH_CHECK(input2.size(0) == B && input2.size(1) == 2 && input2.size(2) == H && input2.size(3) == W, op,
@@ -59,13 +73,22 @@ int resample2d_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &
     TORCH_CHECK(gradInput2.sizes() == input2.sizes() && gradInput2.is_contiguous(), op,
                 ": gradInput2 must be contiguous and shaped like input2");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor flow = input2.contiguous(), go = gradOutput.contiguous();
+    // bfloat16: gradInput1 is accumulated in float32 (never with bfloat16 atomics, which round at every addition) and rounded once
+    at::Tensor img = bf ? input1.to(at::kFloat) : input1;
+    at::Tensor flow = bf ? input2.to(at::kFloat).contiguous() : input2.contiguous();
+    at::Tensor go = bf ? gradOutput.to(at::kFloat).contiguous() : gradOutput.contiguous();
+    at::Tensor g1 = bf ? gradInput1.to(at::kFloat) : gradInput1;
+    at::Tensor g2 = bf ? at::empty(gradInput2.sizes(), gradInput2.options().dtype(at::kFloat)) : gradInput2;
     int64_t is[4];
-    strides4(input1, is);
-    check_rc(fn2_resample2d_backward(input1.data_ptr<float>(), is, flow.data_ptr<float>(), go.data_ptr<float>(),
-                                     gradInput1.data_ptr<float>(), gradInput2.data_ptr<float>(), B, C,
-                                     (int)input1.size(2), (int)input1.size(3), H, W, kernel_size, bilinear ? 1 : 0,
+    strides4(img, is);
+    check_rc(fn2_resample2d_backward(img.data_ptr<float>(), is, flow.data_ptr<float>(), go.data_ptr<float>(),
+                                     g1.data_ptr<float>(), g2.data_ptr<float>(), B, C,
+                                     (int)img.size(2), (int)img.size(3), H, W, kernel_size, bilinear ? 1 : 0,
                                      current_stream(input1)), op);
+    if (bf) {
+        gradInput1.copy_(g1);
+        gradInput2.copy_(g2);
+    }
     return 1;
 }
 

@@ -7,7 +7,10 @@
 // Layout: NCHW; one lane owns VEC consecutive pixels of one image and walks the channel
 // planes (plane stride H*W), so every wave access is a fully coalesced 16 B/lane segment.
 // Arithmetic follows the reference exactly: square in T, accumulate and sqrt in float (fwd);
-// float product divided in double by (float(out) + 1e-9) (bwd).
+// float product divided in double by (float(out) + 1e-9) (bwd).  bfloat16 (not a type of the reference): the square of a bf16
+// value is exact in fp32 and is summed there, so the result is rounded once; the backward runs on the float-widened values.
+#include <type_traits>
+
 #include "fn2_common.h"
 
 namespace fn2 {
@@ -16,6 +19,14 @@ template <typename T> struct VecOf;
 template <> struct VecOf<float> { typedef float __attribute__((ext_vector_type(4))) type; static constexpr int N = 4; };
 template <> struct VecOf<half_t> { typedef half_t __attribute__((ext_vector_type(8))) type; static constexpr int N = 8; };
 template <> struct VecOf<double> { typedef double __attribute__((ext_vector_type(2))) type; static constexpr int N = 2; };
+template <> struct VecOf<bf16_t> { typedef bf16_t __attribute__((ext_vector_type(8))) type; static constexpr int N = 8; };
+
+// one term of the forward's sum: the square rounded to T as the reference does (:56), except for bf16, whose square is exact in fp32
+template <typename T> __device__ __forceinline__ float chnorm_sq(T v)
+{
+    if constexpr (std::is_same<T, bf16_t>::value) return (float)v * (float)v;
+    else return (float)(T)(v * v);
+}
 
 // ---------------------------------------------------------------- forward
 // grid-stride over "pixel groups" of N pixels; HW % N == 0 guaranteed by the launcher.
@@ -35,10 +46,7 @@ __global__ __launch_bounds__(256) void chnorm_fwd_vec(const T *__restrict__ in, 
         for (int c = 0; c < C; ++c) {
             const V v = *reinterpret_cast<const V *>(src + (long)c * HW);
 #pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const T sq = v[i] * v[i];     // square in T (:56)
-                acc[i] = acc[i] + (float)sq;  // float accumulation (:51,:56)
-            }
+            for (int i = 0; i < N; ++i) acc[i] = acc[i] + chnorm_sq<T>(v[i]);   // float accumulation (:51,:56)
         }
         V o;
 #pragma unroll
@@ -56,9 +64,7 @@ __global__ __launch_bounds__(256) void chnorm_fwd_scalar(const T *__restrict__ i
         const T *src = in + b * C * HW + p;
         float acc = 0.0f;
         for (int c = 0; c < C; ++c) {
-            const T v = src[(long)c * HW];
-            const T sq = v * v;
-            acc = acc + (float)sq;
+            acc = acc + chnorm_sq<T>(src[(long)c * HW]);
         }
         out[g] = (T)__fsqrt_rn(acc);
     }
@@ -172,6 +178,7 @@ extern "C" int fn2_channelnorm_forward(const void *in, void *out, int dtype, int
     switch (dtype) {
     case FN2_F32: return chnorm_fwd_launch<float>(in, out, B, C, H, W, s);
     case FN2_F16: return chnorm_fwd_launch<half_t>(in, out, B, C, H, W, s);
+    case FN2_BF16: return chnorm_fwd_launch<bf16_t>(in, out, B, C, H, W, s);
     default: return chnorm_fwd_launch<double>(in, out, B, C, H, W, s);
     }
 }
@@ -191,6 +198,7 @@ extern "C" int fn2_channelnorm_backward(const void *in, const void *out, const v
     switch (dtype) {
     case FN2_F32: return chnorm_bwd_launch<float>(in, out, grad_out, gout_strides, grad_in, B, C, H, W, s);
     case FN2_F16: return chnorm_bwd_launch<half_t>(in, out, grad_out, gout_strides, grad_in, B, C, H, W, s);
+    case FN2_BF16: return chnorm_bwd_launch<bf16_t>(in, out, grad_out, gout_strides, grad_in, B, C, H, W, s);
     default: return chnorm_bwd_launch<double>(in, out, grad_out, gout_strides, grad_in, B, C, H, W, s);
     }
 }

@@ -26,13 +26,15 @@ int corr_forward_f16x2(const float *in1, const float *in2, float *out, long out_
 int corr_forward_f16x2_wide(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H, int W,
                             hipStream_t s);   // W > 64 (correlation_f16x2_wide.hip)
 
-// half tensors (correlation_f16_fwd.hip): one f16 MFMA per block product, no split
+// half and bfloat16 tensors (dtype FN2_F16 / FN2_BF16; correlation_f16_fwd.hip): one 16-bit MFMA per block product, no split
 bool corr_f16_fwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_f16(const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W, hipStream_t s);
+int corr_forward_f16(int dtype, const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W,
+                     hipStream_t s);
 
-// half tensors, backward (correlation_f16_bwd.hip): one f16 MFMA per product, fp32 sums
+// half and bfloat16 tensors, backward (correlation_f16_bwd.hip): one 16-bit MFMA per product, fp32 sums
 bool corr_f16_bwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_backward_f16(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W, hipStream_t s);
+int corr_backward_f16(int dtype, const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W,
+                      hipStream_t s);
 
 void corr_f16x2_set_debug_buffer(void *p);
 void *corr_f16x2_get_debug_buffer();

@@ -1,5 +1,5 @@
 // correlation_direct.hip -- parameter-general correlation kernels (any pad / kernel_size /
-// max_displacement / strides, f32 / f16 / f64) for gfx950.
+// max_displacement / strides, f32 / f16 / f64 / bf16) for gfx950.
 //
 // Replaces the arithmetic of the reference's channels_first + correlation_forward
 // (correlation_cuda_kernel.cu:46-70, :73-147) and correlation_backward_input1/2 (:150-241,
@@ -9,11 +9,14 @@
 // a wave read one contiguous run of in1 and one (shifted) contiguous run of in2 -- coalesced
 // without any transpose.  The accumulator is fp32 for every dtype, as in the reference
 // forward (:112,:124); the backward accumulates in fp32 (f32, f16) or fp64 (f64) -- the
-// reference accumulates f16 in f16 there (:229), this is the more accurate superset.
+// reference accumulates f16 in f16 there (:229), this is the more accurate superset.  bf16 (not a type of the reference): the
+// products of two bf16 values are formed in fp32, where they are exact, like those of the bf16 matrix kernels.
 //
 // Where the reference reads outside its padded buffers (kernel_size > 1 with
 // md - (md/s2)*s2 < (k-1)/2, or pad < the displacement reach in the backward), those reads
 // are defined as 0 here (the CPU checker under tests/ defines them the same way).
+#include <type_traits>
+
 #include "corr_params.h"
 
 namespace fn2 {
@@ -21,6 +24,13 @@ namespace fn2 {
 
 template <typename T> struct Acc { typedef float type; };
 template <> struct Acc<double> { typedef double type; };
+
+// one product of the forward: in T (:124), except for bf16 (exact in fp32)
+template <typename T> __device__ __forceinline__ float fwd_prod(T a, T b)
+{
+    if constexpr (std::is_same<T, bf16_t>::value) return (float)a * (float)b;
+    else return (float)(T)(a * b);
+}
 
 // ---------------------------------------------------------------- forward
 template <typename T>
@@ -53,13 +63,12 @@ __global__ __launch_bounds__(256) void corr_fwd_direct(const T *__restrict__ in1
                 float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f; // 4 independent chains for ILP
                 int c = 0;
                 for (; c + 4 <= p.C; c += 4) {
-                    const T p0 = pa[(long)(c + 0) * HW] * pb[(long)(c + 0) * HW]; // product in T (:124)
-                    const T p1 = pa[(long)(c + 1) * HW] * pb[(long)(c + 1) * HW];
-                    const T p2 = pa[(long)(c + 2) * HW] * pb[(long)(c + 2) * HW];
-                    const T p3 = pa[(long)(c + 3) * HW] * pb[(long)(c + 3) * HW];
-                    s0 += (float)p0; s1 += (float)p1; s2 += (float)p2; s3 += (float)p3;
+                    s0 += fwd_prod<T>(pa[(long)(c + 0) * HW], pb[(long)(c + 0) * HW]);
+                    s1 += fwd_prod<T>(pa[(long)(c + 1) * HW], pb[(long)(c + 1) * HW]);
+                    s2 += fwd_prod<T>(pa[(long)(c + 2) * HW], pb[(long)(c + 2) * HW]);
+                    s3 += fwd_prod<T>(pa[(long)(c + 3) * HW], pb[(long)(c + 3) * HW]);
                 }
-                for (; c < p.C; ++c) s0 += (float)(T)(pa[(long)c * HW] * pb[(long)c * HW]);
+                for (; c < p.C; ++c) s0 += fwd_prod<T>(pa[(long)c * HW], pb[(long)c * HW]);
                 acc += (s0 + s1) + (s2 + s3);
             }
         }
@@ -186,6 +195,7 @@ int corr_forward_direct(const void *in1, const void *in2, void *out, int dtype, 
     case FN2_F32: return fwd_direct_launch<float>(in1, in2, out, p, s);
     case FN2_F16: return fwd_direct_launch<half_t>(in1, in2, out, p, s);
     case FN2_F64: return fwd_direct_launch<double>(in1, in2, out, p, s);
+    case FN2_BF16: return fwd_direct_launch<bf16_t>(in1, in2, out, p, s);
     default: return FN2_EDTYPE;
     }
 }
@@ -197,6 +207,7 @@ int corr_backward_direct(const void *in1, const void *in2, const void *gout, voi
     case FN2_F32: return bwd_direct_launch<float>(in1, in2, gout, g1, g2, p, s);
     case FN2_F16: return bwd_direct_launch<half_t>(in1, in2, gout, g1, g2, p, s);
     case FN2_F64: return bwd_direct_launch<double>(in1, in2, gout, g1, g2, p, s);
+    case FN2_BF16: return bwd_direct_launch<bf16_t>(in1, in2, gout, g1, g2, p, s);
     default: return FN2_EDTYPE;
     }
 }

@@ -21,6 +21,9 @@
 // fma chain over its own window (exact_grad), as in the fp32 kernel.
 // FlowNetC's configuration (kernel_size 1, stride1 1, stride2 2, pad == max_displacement == 20), maps up to 64 pixels wide, C % 64 == 0,
 // H even, W % 8 == 0, 16-byte aligned tensors; other half shapes take the general kernel (correlation_direct.hip).
+// BFLOAT16 tensors: the same kernel instantiated on the element type E (fn2::Op16): v_mfma_f32_16x16x32_bf16 (the f16 instruction's
+// layouts and cycles), G widened to fp32 by the staging waves and packed back exactly with v_cvt_pk_bf16_f32, the result rounded
+// once with that conversion.
 #include <type_traits>
 
 #include "corr_params.h"
@@ -34,8 +37,6 @@ namespace hbh {
 constexpr int ABL = FN2_HBH_ABL;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
 #define FN2_LDS(T) __attribute__((address_space(3))) T
@@ -57,10 +58,10 @@ constexpr int E_BYTES = CG * 4 * 64 * 4;          // epilogue image [64 channels
 constexpr int X_OFS = GIMG, LDS_BYTES = X_OFS + E_BYTES;
 static_assert(2 * XBUF <= E_BYTES && LDS_BYTES <= 163840, "LDS budget");
 
-struct Args {
-    const _Float16 *nbr[2];   // [0] = in2 (neighbours for gradInput1), [1] = in1 (for gradInput2)
-    const _Float16 *gout;
-    _Float16 *gin[2];         // [0] = gradInput1, [1] = gradInput2
+template <class E> struct Args {   // E: half_t or bf16_t
+    const E *nbr[2];          // [0] = in2 (neighbours for gradInput1), [1] = in1 (for gradInput2)
+    const E *gout;
+    E *gin[2];                // [0] = gradInput1, [1] = gradInput2
     int B, C, H, W;           // H even, W % 8 == 0, W <= 64, C % 64 == 0
     int NRG, NCGR;            // row groups per parity, channel groups
     float fC, rC;             // (float)C and 1 / C: kernel arguments so that they are SGPRs
@@ -91,18 +92,12 @@ __device__ __forceinline__ void static_for(F &&f)
     }
 }
 
-__device__ __forceinline__ unsigned pk_f16(float a, float b)   // v_cvt_pk_f16_f32, round to nearest even
-{
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f2v){a, b}, h2));
-}
-
 // one gradient element as a plain fp32 fma chain over its own displacement window (cold path: non-finite matrix results)
-__device__ __forceinline__ float exact_grad(const Args &p, int flip, int n, int c, int y, int x)
+template <class E> __device__ __forceinline__ float exact_grad(const Args<E> &p, int flip, int n, int c, int y, int x)
 {
     const long HW = (long)p.H * p.W;
-    const _Float16 *X = p.nbr[flip] + ((long)n * p.C + c) * HW;
-    const _Float16 *g = p.gout + (long)n * D * D * HW;
+    const E *X = p.nbr[flip] + ((long)n * p.C + c) * HW;
+    const E *g = p.gout + (long)n * D * D * HW;
     float s = 0.0f;
     for (int tj = 0; tj < D; ++tj)
         for (int ti = 0; ti < D; ++ti) {
@@ -121,8 +116,10 @@ constexpr int NGL = 12;                     // G loads per lane and u: 4 neighbo
 struct XSet { u4 v[XK]; };
 struct GSet { u4 v[NGL]; };
 
-__global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
+template <class E>
+__global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
 {
+    typedef typename Op16<E>::v8 h8;   // 8 elements of E: an MFMA fragment, or one 16-byte load of gradOutput
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
         auto finish = [&](f4 val) -> u2 {
             if (pow2) { val[0] *= r; val[1] *= r; val[2] *= r; val[3] *= r; }
             else { val[0] /= f; val[1] /= f; val[2] /= f; val[3] /= f; }
-            return (u2){pk_f16(val[0], val[1]), pk_f16(val[2], val[3])};
+            return (u2){Op16<E>::pk(val[0], val[1]), Op16<E>::pk(val[2], val[3])};
         };
         unsigned bad = 0;
 #pragma unroll
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
         // allocator reused a destination of one arm's loads as an address temporary of the other and had to wait for vmcnt(0) --
         // for everything just requested -- at the join.)
         auto x_issue = [&](XSet &L, const Task &tk, int u, int ch, bool valid) {
-            const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.nbr[tk.flip] + (long)tk.n * p.C * HW), 0, xbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.nbr[tk.flip] + (long)tk.n * p.C * HW), 0, xbytes, 0x00020000);
             const int il = 4 * tk.rg - DR + 4 * u + s_row;
             const bool ok = valid && il >= 0 && il < HL && 8 * s_piece < p.W;
             const unsigned vo = ok ? (unsigned)((s_ch * hw + (2 * il + tk.py) * p.W + 8 * s_piece) * 2) : 0x80000000u;
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
         // hit 64 distinct banks; the first version (two ti, four bi, eight pieces per instruction) was 4- to 8-way conflicted there and
         // the conversion took 33 of the kernel's 77 us (ablations: scripts/half_bwd_abl.sh).
         auto g_issue = [&](GSet &S, const Task &tk, int u, bool valid) {
-            const __amdgpu_buffer_rsrc_t rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.gout + (long)tk.n * D * D * HW), 0, gbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.gout + (long)tk.n * D * D * HW), 0, gbytes, 0x00020000);
             int ln = lane;
             asm volatile("" : "+v"(ln));
             const int ts = ln >> 3, pc = ln & 7, ai = w8;
@@ -401,7 +398,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
                             }
                             w[s] = v;
                         });
-                        const u4 vh = {pk_f16(w[0], w[1]), pk_f16(w[2], w[3]), pk_f16(w[4], w[5]), pk_f16(w[6], w[7])};
+                        const u4 vh = {Op16<E>::pk(w[0], w[1]), Op16<E>::pk(w[2], w[3]), Op16<E>::pk(w[4], w[5]), Op16<E>::pk(w[6], w[7])};
                         gh[fi] = __builtin_bit_cast(h8, vh);
                         __builtin_amdgcn_sched_barrier(0);   // one operand at a time: 8 loads in flight
                     }
@@ -422,8 +419,8 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
                     if (ABL & 1) { asm volatile("" ::"v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3])); return; }
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) {
-                        if constexpr (f0 >= 0) acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x[ct], gh[f0 >= 0 ? f0 : 0], acc[0][ct], 0, 0, 0);
-                        if constexpr (f1 >= 0) acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x[ct], gh[f1 >= 0 ? f1 : 0], acc[1][ct], 0, 0, 0);
+                        if constexpr (f0 >= 0) acc[0][ct] = Op16<E>::mfma(x[ct], gh[f0 >= 0 ? f0 : 0], acc[0][ct]);
+                        if constexpr (f1 >= 0) acc[1][ct] = Op16<E>::mfma(x[ct], gh[f1 >= 0 ? f1 : 0], acc[1][ct]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -501,21 +498,22 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args p)
 
 bool corr_f16_bwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
 {
-    if (dtype != FN2_F16) return false;
+    if (dtype != FN2_F16 && dtype != FN2_BF16) return false;
     if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md != 2 * hbh::DR) return false;
     if (C % hbh::CG != 0 || C < hbh::CG || (H & 1) || (W % 8) != 0 || W > 64) return false;
     if ((long)C * H * W * 2 >= 0x7fffffffL || (long)hbh::D * hbh::D * H * W * 2 >= 0x7fffffffL) return false;   // 32-bit byte offsets
     return true;
 }
 
-// in1, in2, gout, g1, g2: half tensors
-int corr_backward_f16(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W, hipStream_t s)
+// in1, in2, gout, g1, g2: tensors of element type E (half or bfloat16)
+template <class E>
+static int corr_backward_16(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W, hipStream_t s)
 {
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(gout, 16) || !aligned(g1, 16) || !aligned(g2, 16)) return FN2_EALIGN;
-    hbh::Args a;
-    a.nbr[0] = static_cast<const _Float16 *>(in2); a.nbr[1] = static_cast<const _Float16 *>(in1);
-    a.gout = static_cast<const _Float16 *>(gout);
-    a.gin[0] = static_cast<_Float16 *>(g1); a.gin[1] = static_cast<_Float16 *>(g2);
+    hbh::Args<E> a;
+    a.nbr[0] = static_cast<const E *>(in2); a.nbr[1] = static_cast<const E *>(in1);
+    a.gout = static_cast<const E *>(gout);
+    a.gin[0] = static_cast<E *>(g1); a.gin[1] = static_cast<E *>(g2);
     a.B = B; a.C = C; a.H = H; a.W = W;
     a.NRG = (H / 2 + 3) / 4; a.NCGR = C / hbh::CG;
     a.fC = (float)C; a.rC = 1.0f / (float)C;
@@ -523,8 +521,15 @@ int corr_backward_f16(const void *in1, const void *in2, const void *gout, void *
     if (ntasks == 0) return FN2_OK;
     if (ntasks > 0x3fffffffL) return FN2_EINVAL;
     const unsigned grid = ntasks < 256 ? (unsigned)ntasks : 256u;   // persistent: one workgroup per CU
-    hipLaunchKernelGGL(hbh::corr_bwd_f16, dim3(grid), dim3(hbh::NWAVES * 64), 0, s, a);
+    hipLaunchKernelGGL(hbh::corr_bwd_f16<E>, dim3(grid), dim3(hbh::NWAVES * 64), 0, s, a);
     return launch_status();
+}
+
+int corr_backward_f16(int dtype, const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W,
+                      hipStream_t s)
+{
+    if (dtype == FN2_BF16) return corr_backward_16<bf16_t>(in1, in2, gout, g1, g2, B, C, H, W, s);
+    return corr_backward_16<half_t>(in1, in2, gout, g1, g2, B, C, H, W, s);
 }
 
 } // namespace fn2

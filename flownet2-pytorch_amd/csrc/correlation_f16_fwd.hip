@@ -18,18 +18,24 @@
 //   - no out-of-range path: every half value, inf and nan included, is its own matrix operand.
 // C % 128 == 0 (an even number of steps), H even, W % 8 == 0, 16-byte aligned tensors; other half shapes take the general
 // kernel (correlation_direct.hip).  Maps wider than 64 pixels: the windowed variant at the end of this file.
+// BFLOAT16 tensors run the same two kernels, instantiated on the element type E (fn2::Op16, fn2_common.h): v_mfma_f32_16x16x32_bf16
+// has the f16 instruction's lane layout, cycles and C/D layout on gfx950, the staging moves 16-bit values without looking at them,
+// ds_read_b64_tr_b16 is type-agnostic, and the epilogue rounds once with v_cvt_pk_bf16_f32 (not the integer +0x7FFF rounding,
+// which turns some NaNs into zero or infinity).  Products of two bf16 values are exact in fp32 too; bf16 has fp32's exponent
+// range, so there is no out-of-range path either.
 #include "f16x2_common.h"
 
 namespace fn2 {
 namespace hh {
 using namespace hf;
 
-typedef ArgsT<_Float16> ArgsH;
 constexpr int CKH = 2 * CK;                       // channels per step
 struct LoadSetH { u4 a[4], b[4]; };               // one step of one lane: slot k = channels 16k .. 16k+15, 8 pixels (16 B) each tile
 
-__global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsH p)
+template <class E>
+__global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsT<E> p)
 {
+    typedef typename Op16<E>::v8 h8;   // the fragment: 8 elements of E
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -92,7 +98,7 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsH p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) val[e] = val[e] > 0.0f ? val[e] : val[e] * sl;
             }
-            const u2 packed = {pk_f16(val[0], val[1]), pk_f16(val[2], val[3])};
+            const u2 packed = {Op16<E>::pk(val[0], val[1]), Op16<E>::pk(val[2], val[3])};
             __builtin_amdgcn_raw_buffer_store_b64(packed, rso, (int)v, so0 + 4 * i * (int)(HW * 2), 2);
         }
     };
@@ -116,8 +122,8 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsH p)
             const bool s_okb = valid && (s_ilb >= 0) && (s_ilb < HL) && (s_x < p.W);
             v_offa = s_oka ? (unsigned)((s_ch * HW + (long)(2 * s_ila + tk.py) * p.W + s_x) * 2) : 0x80000000u;
             v_offb = s_okb ? (unsigned)((s_ch * HW + (long)(2 * s_ilb + tk.py) * p.W + s_x) * 2) : 0x80000000u;
-            rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.in1 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
-            rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.in2 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
+            rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.in1 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
+            rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.in2 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
         };
         auto issue_loads = [&](LoadSetH &L, int c0) {   // rows outside the image: out-of-range offset, the load returns zeros
 #pragma unroll
@@ -211,7 +217,7 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsH p)
                 static_for<0, NAB>([&](auto abc) {
                     constexpr int ab = decltype(abc)::value;
                     constexpr int pi = pair_idx(R, ab, m);
-                    if constexpr (pi >= 0) acc[pi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[jj & 1], a[ab], acc[pi], 0, 0, 0);
+                    if constexpr (pi >= 0) acc[pi] = Op16<E>::mfma(b[jj & 1], a[ab], acc[pi]);
                 });
                 __builtin_amdgcn_sched_barrier(0);   // fragments one block ahead, not all of them (register budget)
             });
@@ -283,15 +289,17 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16(ArgsH p)
 // they meet, in the same 16 block slots per channel row; lanes re-mapped so that every load instruction has one source tensor)
 // with this file's half staging and single product.  7 block pairs x 2 channel halves = 14 MFMAs per matrix wave and step.
 constexpr int AW = 4, NB = 7, WPX = 8 * AW;
-struct ArgsHW : ArgsH {
+template <class E> struct ArgsHW : ArgsT<E> {
     int NXQ;                     // column windows: ceil(W / 32)
     unsigned magic_x;            // ceil(2^32 / NXQ)
 };
 struct TaskW { int n, py, rg, u, xq; };
 struct LoadSetHW { u4 a[2], b0[2], b1[4]; };   // [channel half] of A' and of B' 0..3, [slot] of B' 4..11
 
-__global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW p)
+template <class E>
+__global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW<E> p)
 {
+    typedef typename Op16<E>::v8 h8;
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -356,7 +364,7 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) val[e] = val[e] > 0.0f ? val[e] : val[e] * sl;
             }
-            const u2 packed = {pk_f16(val[0], val[1]), pk_f16(val[2], val[3])};
+            const u2 packed = {Op16<E>::pk(val[0], val[1]), Op16<E>::pk(val[2], val[3])};
             __builtin_amdgcn_raw_buffer_store_b64(packed, rso, (int)v, so0 + 8 * i * (int)(HW * 2), 2);
         }
     };
@@ -380,8 +388,8 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW p)
             v_offa = (valid && ila < HL && xa < p.W) ? (unsigned)((a_ch * HW + (long)(2 * ila + tk.py) * p.W + xa) * 2) : 0x80000000u;
             v_offb0 = (okb && xb0 >= 0 && xb0 < p.W) ? (unsigned)((a_ch * HW + (long)(2 * ilb + tk.py) * p.W + xb0) * 2) : 0x80000000u;
             v_offb1 = (okb && s_piece < 6 && xb1 < p.W) ? (unsigned)((s_ch * HW + (long)(2 * ilb + tk.py) * p.W + xb1) * 2) : 0x80000000u;
-            rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.in1 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
-            rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(p.in2 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
+            rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.in1 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
+            rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<E *>(p.in2 + (long)tk.n * p.C * HW), 0, nbytes, 0x00020000);
         };
         auto issue_loads = [&](LoadSetHW &L, int c0) {
 #pragma unroll
@@ -471,7 +479,7 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW p)
             static_for<0, NB>([&](auto jc) {
                 constexpr int jj = decltype(jc)::value;
                 if constexpr (jj + 1 < NB) b[(jj + 1) & 1] = frag(cur, AW + R + jj + 1, hfi);
-                acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[jj & 1], a, acc[jj], 0, 0, 0);
+                acc[jj] = Op16<E>::mfma(b[jj & 1], a, acc[jj]);
             });
         });
     };
@@ -521,7 +529,7 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW p)
 
 bool corr_f16_fwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
 {
-    if (dtype != FN2_F16) return false;
+    if (dtype != FN2_F16 && dtype != FN2_BF16) return false;
     if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md / 2 != hf::DR || (md & 1)) return false;
     if (C % (2 * hh::CKH) != 0 || (H & 1) || (W % 8) != 0) return false;
     if ((long)C * H * W * 2 >= 0x7fffffffL) return false;   // 32-bit buffer offsets per batch item
@@ -529,12 +537,13 @@ bool corr_f16_fwd_applicable(int dtype, int C, int H, int W, int pad, int k, int
     return true;
 }
 
-// in1, in2, out: half tensors; out_bs in elements
-int corr_forward_f16(const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W, hipStream_t s)
+// in1, in2, out: tensors of element type E (half or bfloat16); out_bs in elements
+template <class E>
+static int corr_forward_16(const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W, hipStream_t s)
 {
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(out, 16) || (out_bs % 4) != 0) return FN2_EALIGN;
-    hh::ArgsHW a;
-    a.in1 = static_cast<const _Float16 *>(in1); a.in2 = static_cast<const _Float16 *>(in2); a.out = static_cast<_Float16 *>(out);
+    hh::ArgsHW<E> a;
+    a.in1 = static_cast<const E *>(in1); a.in2 = static_cast<const E *>(in2); a.out = static_cast<E *>(out);
     a.out_bs = out_bs; a.slope = slope;
     a.fC = (float)C; a.rC = 1.0f / (float)C;
     a.B = B; a.C = C; a.H = H; a.W = W;
@@ -548,9 +557,16 @@ int corr_forward_f16(const void *in1, const void *in2, void *out, long out_bs, f
     if (ntasks == 0) return FN2_OK;
     const long per_stream = (ntasks + 7) / 8;
     const int G = per_stream < 32 ? (int)per_stream : 32;
-    if (W > 64) hipLaunchKernelGGL(hh::corr_fwd_f16_wide, dim3(8u * G), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL(hh::corr_fwd_f16, dim3(8u * G), dim3(1024), 0, s, static_cast<const hh::ArgsH &>(a));
+    if (W > 64) hipLaunchKernelGGL(hh::corr_fwd_f16_wide<E>, dim3(8u * G), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(hh::corr_fwd_f16<E>, dim3(8u * G), dim3(1024), 0, s, static_cast<const hf::ArgsT<E> &>(a));
     return launch_status();
+}
+
+int corr_forward_f16(int dtype, const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W,
+                     hipStream_t s)
+{
+    if (dtype == FN2_BF16) return corr_forward_16<bf16_t>(in1, in2, out, out_bs, slope, B, C, H, W, s);
+    return corr_forward_16<half_t>(in1, in2, out, out_bs, slope, B, C, H, W, s);
 }
 
 } // namespace fn2

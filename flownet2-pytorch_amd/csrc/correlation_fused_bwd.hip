@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void mask_slice_kernel(const T *__restrict__ g
     const long total = (long)B * n_item;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long n = i / n_item, r = i - n * n_item;
-        // the test in T (a stored double below the float range must not read as zero), the product in fp32 for half and
+        // the test in T (a stored double below the float range must not read as zero), the product in fp32 for half, bfloat16 and
         // float tensors (what leaky_relu_backward computes) and in double for double ones
         typedef typename std::conditional<std::is_same<T, double>::value, double, float>::type op_t;
         const T o = out[n * obs + r];
@@ -102,6 +102,7 @@ extern "C" int fn2_correlation_backward_fused(const void *in1, const void *in2, 
                        n_item, B, negative_slope)
         if (dtype == FN2_F32) FN2_MASK(float);
         else if (dtype == FN2_F16) FN2_MASK(half_t);
+        else if (dtype == FN2_BF16) FN2_MASK(bf16_t);
         else FN2_MASK(double);
 #undef FN2_MASK
     }

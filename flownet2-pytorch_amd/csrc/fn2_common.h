@@ -10,6 +10,7 @@
 namespace fn2 {
 
 typedef _Float16 half_t;
+typedef __bf16 bf16_t;
 
 static inline int launch_status()
 {
@@ -25,6 +26,7 @@ static inline size_t dtype_size(int dtype)
     case FN2_F32: return 4;
     case FN2_F16: return 2;
     case FN2_F64: return 8;
+    case FN2_BF16: return 2;
     default: return 0;
     }
 }
@@ -50,6 +52,31 @@ template <class V> __device__ __forceinline__ void store_out(V *p, V v)
     else *p = v;
 #endif
 }
+
+// The two 16-bit matrix operand types (half, bfloat16) of the single-product correlation kernels: the 8-element fragment of
+// v_mfma_f32_16x16x32_{f16,bf16} (same lane layout, same cycles, same C/D layout on gfx950) and the packed conversion of two fp32
+// results (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN).
+template <class E> struct Op16;
+template <> struct Op16<half_t> {
+    typedef half_t v8 __attribute__((ext_vector_type(8)));
+    typedef half_t v2 __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ float __attribute__((ext_vector_type(4)))
+    mfma(v8 a, v8 b, float __attribute__((ext_vector_type(4))) c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ unsigned pk(float a, float b)
+    {
+        return __builtin_bit_cast(unsigned, __builtin_convertvector((float __attribute__((ext_vector_type(2)))){a, b}, v2));
+    }
+};
+template <> struct Op16<bf16_t> {
+    typedef bf16_t v8 __attribute__((ext_vector_type(8)));
+    typedef bf16_t v2 __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ float __attribute__((ext_vector_type(4)))
+    mfma(v8 a, v8 b, float __attribute__((ext_vector_type(4))) c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ unsigned pk(float a, float b)
+    {
+        return __builtin_bit_cast(unsigned, __builtin_convertvector((float __attribute__((ext_vector_type(2)))){a, b}, v2));
+    }
+};
 
 // ChannelNorm's gradient of one element (channelnorm_kernel.cu:93):
 // static_cast<float>(gO) * static_cast<float>(x) / (static_cast<float>(out) + 1e-9) -- float product, double divide, rounded to float.

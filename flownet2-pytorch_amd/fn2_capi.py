@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip.so")
 DEBUG_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_debug.so")   # same kernels + fn2_debug_* (csrc/fn2_debug.h)
 
-FN2_F32, FN2_F16, FN2_F64 = 0, 1, 2
+FN2_F32, FN2_F16, FN2_F64, FN2_BF16 = 0, 1, 2, 3
 FN2_CORR_AUTO, FN2_CORR_DIRECT, FN2_CORR_MFMA_F32, FN2_CORR_MFMA_BF16X3, FN2_CORR_MFMA_F16X2 = 0, 1, 2, 3, 4
 
 EXPORTS = [
@@ -77,7 +77,7 @@ def check(rc, what):
 
 def _dtype_code(t):
     import torch
-    return {torch.float32: FN2_F32, torch.float16: FN2_F16, torch.float64: FN2_F64}[t.dtype]
+    return {torch.float32: FN2_F32, torch.float16: FN2_F16, torch.float64: FN2_F64, torch.bfloat16: FN2_BF16}[t.dtype]
 
 
 def _p(t):

@@ -10,6 +10,10 @@ first two, which build the 12-channel input of the next sub-network, are the fus
 ``half()``: the convolution stacks run in fp16; Resample2d / ChannelNorm keep fp32 operands (the reference wraps the custom layers
 in tofp32 / tofp16, models.py:44-49; its resample kernels are float-only), the cost volume of the no-grad path takes the half
 features directly (one f16 MFMA per block product, fused LeakyReLU + concat, half output).
+
+``torch.autocast("cuda", dtype=torch.bfloat16)``: the convolutions run in bf16 and FlowNetC's cost volume takes the bf16 features
+as they are, with and without gradients (v_mfma_f32_16x16x32_bf16, csrc/correlation_f16_fwd.hip / _bwd.hip); the warp groups
+widen to fp32 as for half.
 """
 import torch
 from torch import nn
@@ -159,10 +163,12 @@ class FlowNetCCore(_Refiner):                        # networks/FlowNetC.py:13-1
         redir = self.conv_redir(c3a)
         dt = c3a.dtype
         if not torch.is_grad_enabled():
-            if dt == torch.float16:      # half tensors are matrix operands as they are (csrc/correlation_f16_fwd.hip): no casts
+            if dt in (torch.float16, torch.bfloat16):   # 16-bit tensors are matrix operands as they are (csrc/correlation_f16_fwd.hip)
                 merged = self.corr_fused(c3a.contiguous(), c3b.contiguous(), redir)
             else:
                 merged = self.corr_fused(c3a.float(), c3b.float(), redir.float()).to(dt)
+        elif dt == torch.bfloat16:       # bf16 autocast training: the bf16 kernels forward and backward, no fp32 round trip
+            merged = torch.cat((redir, self.corr_activation(self.corr(c3a, c3b))), 1)
         else:
             merged = torch.cat((redir, self.corr_activation(self.corr(c3a.float(), c3b.float()).to(dt))), 1)
         c3_1 = self.conv3_1(merged)

@@ -3,7 +3,7 @@
 Module names and parameter shapes are the reference's, so a reference checkpoint's ``state_dict`` loads unchanged
 (``conv1.0.weight`` ... ``upsampled_flow3_to_2.bias``, 39 175 298 parameters; tests/test_harness.py compares the key set
 with the reference's own class where the reference checkout is present).  The cost volume is this repo's
-``Correlation`` (HIP kernels, fp32); the LeakyReLU + concat around it are fused into the correlation's epilogue
+``Correlation`` (HIP kernels, fp32; bf16 under ``torch.autocast(dtype=torch.bfloat16)``, where conv3 hands it bf16 features); the LeakyReLU + concat around it are fused into the correlation's epilogue
 (``CorrelationLeakyReLUCat``) -- in training too since round 4: the backward reads the activation's derivative
 off the sign of the stored output and the gradient from its slice of the concat gradient (``fused_training=False`` keeps the
 three separate ops of FlowNetC.py:86-92).

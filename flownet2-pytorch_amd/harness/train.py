@@ -1,6 +1,7 @@
 """FlowNet2C training / inference steps on synthetic data (reference main.py:246-340 with
 MultiScale L1 and Adam lr 1e-4, README.md:81-84).  One process per GPU; ``python -m torch.distributed.run
 --nproc-per-node N bench.py --model`` drives it through bench.py."""
+import contextlib
 import time
 
 import torch
@@ -20,9 +21,12 @@ def synthetic_batch(batch, height, width, device, seed=0, rgb_max=255.0):
 
 
 class Trainer:
-    def __init__(self, device, lr=1e-4, seed=1, bucket_bytes=48 << 20):
+    def __init__(self, device, lr=1e-4, seed=1, bucket_bytes=48 << 20, autocast_dtype=None):
+        """autocast_dtype: None (default) trains in fp32; e.g. torch.bfloat16 runs the forward and the loss under
+        torch.autocast(device.type, dtype=autocast_dtype) -- weights, gradients and the optimizer stay fp32."""
         torch.manual_seed(seed)
         self.device = device
+        self.autocast_dtype = autocast_dtype
         self.model = FlowNet2C().to(device)
         dist_utils.broadcast_state(self.model, src=0)          # once, not every step (reference: DataParallel)
         self.reducer = BucketedGradAllReduce(self.model, bucket_bytes=bucket_bytes)
@@ -33,7 +37,8 @@ class Trainer:
         self.model.train()
         self.reducer.zero_grad()
         self.reducer.reset()
-        loss, epe = self.criterion(self.model(inputs), target)
+        with self._autocast():
+            loss, epe = self.criterion(self.model(inputs), target)
         loss.backward()                                         # bucket all-reduces start inside
         self.reducer.finish()
         self.opt.step()
@@ -42,7 +47,13 @@ class Trainer:
     @torch.no_grad()
     def infer(self, inputs):
         self.model.eval()
-        return self.model(inputs)
+        with self._autocast():
+            return self.model(inputs)
+
+    def _autocast(self):
+        if self.autocast_dtype is None:
+            return contextlib.nullcontext()
+        return torch.autocast(torch.device(self.device).type, dtype=self.autocast_dtype)
 
 
 def time_steps(fn, steps, warmup, device):

@@ -3,8 +3,9 @@
 Same public names and signatures as the reference wrapper
 (networks/resample2d_package/resample2d.py:5-49): ``Resample2dFunction.apply(input1, input2,
 kernel_size, bilinear)`` and ``Resample2d(kernel_size=1, bilinear=True)``; output shape is
-(B, C_img, H, W) with B, H, W taken from the flow (reference :16-18).  float32 only, as in the
-reference.  Unlike the reference Module (:48) the image is NOT made contiguous first: the HIP
+(B, C_img, H, W) with B, H, W taken from the flow (reference :16-18).  float32, as in the
+reference; bfloat16 tensors (autocast) are widened to float32 around the float32 kernels and each
+result is rounded to bfloat16 once.  Unlike the reference Module (:48) the image is NOT made contiguous first: the HIP
 kernel honours input1's strides, which saves a full copy of the channel slice models.py:133
 passes in.
 """
@@ -111,6 +112,8 @@ class WarpDiffNormCat(nn.Module):
         self.bilinear = bilinear
 
     def forward(self, x, flow):
+        if x.dtype == torch.bfloat16:   # bf16 (autocast): widened around the fp32 kernels, the result rounded to bf16 once
+            return WarpDiffNormCatFunction.apply(x.float(), flow.float(), float(self.div_flow), self.bilinear).to(torch.bfloat16)
         return WarpDiffNormCatFunction.apply(x, flow, float(self.div_flow), self.bilinear)
 
 
@@ -149,6 +152,8 @@ class WarpDiffNorm(nn.Module):
         self.bilinear = bilinear
 
     def forward(self, x, flow):
+        if x.dtype == torch.bfloat16:   # bf16 (autocast): widened around the fp32 kernels, the result rounded to bf16 once
+            return self.forward(x.float(), flow.float()).to(torch.bfloat16)
         if x.requires_grad and torch.is_grad_enabled():
             # the pair itself wants a gradient (not the case in FlowNet2, where it is the input): the unfused layers under autograd
             from networks.channelnorm_package.channelnorm import ChannelNormFunction

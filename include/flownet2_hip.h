@@ -44,12 +44,24 @@ extern "C" {
  * signature and meaning; a caller built against version 1 runs unchanged on a version-2 library. */
 /* 3 (round 6): + fn2_multiscale_loss_fused, fn2_multiscale_scale_grads; fn2_multiscale_workspace_bytes grew by the ticket counter's
  * 64-byte line (callers size their scratch with it, as before).  Additive as well. */
+/* bfloat16 (FN2_BF16 below) came without a version change: only an element-type value was added, which a version-3 caller never
+ * passes.  A caller detects support by getting something other than FN2_EDTYPE back for dtype FN2_BF16. */
 #define FN2_ABI_VERSION 3
 
 /* element types (reference dispatch: AT_DISPATCH_FLOATING_TYPES_AND_HALF for correlation and
  * channelnorm -- correlation_cuda_kernel.cu:386-415, channelnorm_kernel.cu:111,152; float only
  * for resample2d -- resample2d_kernel.cu:221,269,298) */
-enum { FN2_F32 = 0, FN2_F16 = 1, FN2_F64 = 2 };
+enum { FN2_F32 = 0, FN2_F16 = 1, FN2_F64 = 2, FN2_BF16 = 3 };
+/* FN2_BF16 (bfloat16: fp32's exponent range, 8 significant bits) is accepted by the correlation and ChannelNorm entry points
+ * (forward, _ex, _fused, backward, _ex, _fused, _fused_workspace_bytes; fn2_channelnorm_forward / _backward).  The Resample2d,
+ * warp-diff-norm and multiscale entry points stay float32.  Correlation selectors for bf16 tensors are those of half:
+ * FN2_CORR_AUTO and FN2_CORR_MFMA_F16X2 take the bf16 matrix kernels (v_mfma_f32_16x16x32_bf16, the half kernels' tilings) where
+ * half's preconditions hold, FN2_CORR_DIRECT the general kernel; FN2_CORR_MFMA_F32 / _BF16X3 return what they return for half
+ * (FN2_EUNSUPPORTED).  Products of two bf16 values are exact in fp32, sums are fp32, every result is rounded to bf16 once (round
+ * to nearest even; NaN stays NaN).  No split, no block scale, no out-of-range path: inf and nan are ordinary operands.
+ * Subnormal bf16 operands (magnitude < 2^-126) are kept, not flushed, by
+ * v_mfma_f32_16x16x32_bf16: measured on an MI355X (2^-130 x 2^100 gives 2^-30 exactly; tests/test_gpu_bf16.py). */
+/* any other dtype value: FN2_EDTYPE */
 
 enum {
     FN2_OK = 0,
