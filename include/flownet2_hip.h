@@ -59,6 +59,11 @@ enum { FN2_F32 = 0, FN2_F16 = 1, FN2_F64 = 2, FN2_BF16 = 3 };
  * half's preconditions hold, FN2_CORR_DIRECT the general kernel; FN2_CORR_MFMA_F32 / _BF16X3 return what they return for half
  * (FN2_EUNSUPPORTED).  Products of two bf16 values are exact in fp32, sums are fp32, every result is rounded to bf16 once (round
  * to nearest even; NaN stays NaN).  No split, no block scale, no out-of-range path: inf and nan are ordinary operands.
+ * Fused LeakyReLU store (fn2_correlation_forward_fused, half and bf16): the matrix kernels apply the slope in fp32 to acc / C and
+ * round once, T(v > 0 ? v : v * slope); the general kernel rounds the negative value first, as the unfused Correlation +
+ * LeakyReLU pair does, T(v > 0 ? v : float(T(v)) * slope): two roundings on the negative branch.  The half general kernel
+ * also rounds every product to half before the fp32 sum (the reference's forward); its backward sums exact fp32 products.
+ * Pinned element by element in tests/test_gpu_lowp_contract.py.
  * Subnormal bf16 operands (magnitude < 2^-126) are kept, not flushed, by
  * v_mfma_f32_16x16x32_bf16: measured on an MI355X (2^-130 x 2^100 gives 2^-30 exactly; tests/test_gpu_bf16.py). */
 /* any other dtype value: FN2_EDTYPE */
