@@ -15,6 +15,13 @@ static bool widen_bf16(const at::Tensor &t, const char *op)
     return bf;
 }
 
+// torch.use_deterministic_algorithms(True), warn_only included: the backward passes that scatter grad_input1 take the fixed-point entry
+// points (fn2_*_backward_det), whose results do not depend on the order of the additions; the workspace comes from the caching allocator
+static bool deterministic() { return at::globalContext().deterministicAlgorithms(); }
+// straight from the caching allocator of the current device (at::empty would fill it under the deterministic flag; the entry point clears
+// it on the stream itself); released to the allocator when the DataPtr goes, as a temporary tensor is
+static c10::DataPtr det_workspace(size_t bytes) { return c10::GetAllocator(c10::DeviceType::CUDA)->allocate(bytes); }
+
 static void strides4(const at::Tensor &t, int64_t s[4])
 {
     for (int i = 0; i < 4; ++i) s[i] = t.stride(i);
@@ -81,10 +88,19 @@ int resample2d_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &
     at::Tensor g2 = bf ? at::empty(gradInput2.sizes(), gradInput2.options().dtype(at::kFloat)) : gradInput2;
     int64_t is[4];
     strides4(img, is);
-    check_rc(fn2_resample2d_backward(img.data_ptr<float>(), is, flow.data_ptr<float>(), go.data_ptr<float>(),
-                                     g1.data_ptr<float>(), g2.data_ptr<float>(), B, C,
-                                     (int)img.size(2), (int)img.size(3), H, W, kernel_size, bilinear ? 1 : 0,
-                                     current_stream(input1)), op);
+    const int Hi = (int)img.size(2), Wi = (int)img.size(3);
+    if (deterministic()) {   // torch.use_deterministic_algorithms(True) (warn_only too): gradInput1 summed in fixed point
+        const size_t wsb = fn2_resample2d_backward_det_workspace_bytes(B, C, Hi, Wi, H, W, kernel_size);
+        c10::DataPtr ws = det_workspace(wsb);
+        check_rc(fn2_resample2d_backward_det(img.data_ptr<float>(), is, flow.data_ptr<float>(), go.data_ptr<float>(), g1.data_ptr<float>(),
+                                             g2.data_ptr<float>(), B, C, Hi, Wi, H, W, kernel_size, bilinear ? 1 : 0, ws.get(), wsb,
+                                             current_stream(input1)), op);
+    } else {
+        check_rc(fn2_resample2d_backward(img.data_ptr<float>(), is, flow.data_ptr<float>(), go.data_ptr<float>(),
+                                         g1.data_ptr<float>(), g2.data_ptr<float>(), B, C,
+                                         Hi, Wi, H, W, kernel_size, bilinear ? 1 : 0,
+                                         current_stream(input1)), op);
+    }
     if (bf) {
         gradInput1.copy_(g1);
         gradInput2.copy_(g2);
@@ -144,6 +160,15 @@ int warp_diff_norm_cat_backward_hip(at::Tensor &pair, at::Tensor &flow, at::Tens
     }
     c10::DeviceGuard guard(pair.device());
     at::Tensor go = gradOutput.contiguous();
+    if (want_pair && deterministic()) {   // the second image's gradient is scattered: fixed-point sums under the deterministic flag
+        const size_t wsb = fn2_warp_diff_norm_cat_backward_det_workspace_bytes(B, C, H, W);
+        c10::DataPtr ws = det_workspace(wsb);
+        check_rc(fn2_warp_diff_norm_cat_backward_det(pair.data_ptr<float>(), flow.data_ptr<float>(), output.data_ptr<float>(),
+                                                     go.data_ptr<float>(), gradPair.data_ptr<float>(), gradFlow.data_ptr<float>(),
+                                                     (float)div_flow, B, C, H, W, bilinear ? 1 : 0, ws.get(), wsb, current_stream(pair)),
+                 op);
+        return 1;
+    }
     check_rc(fn2_warp_diff_norm_cat_backward(pair.data_ptr<float>(), flow.data_ptr<float>(), output.data_ptr<float>(), go.data_ptr<float>(),
                                              want_pair ? gradPair.data_ptr<float>() : nullptr, gradFlow.data_ptr<float>(), (float)div_flow,
                                              B, C, H, W, bilinear ? 1 : 0, current_stream(pair)), op);

@@ -13,6 +13,7 @@
 // atomics and forms both flow-gradient components from the same loaded corners.
 // Arithmetic order follows the reference so the gather results are bit-identical to its source
 // semantics: bilinear weights in double, each term rounded to float, float accumulation.
+#include <algorithm>
 #include <type_traits>
 
 #include "fn2_common.h"
@@ -42,6 +43,33 @@ __device__ __forceinline__ int d2i_sat(double v)
     if (v <= -2147483648.0) return (-2147483647 - 1);
     return (int)v;
 }
+
+// ---------------------------------------------------------------- deterministic grad_input1: fixed-point accumulation
+// The contract (include/flownet2_hip.h, fn2_resample2d_backward_det): per plane (b, c) of the scattered gradient, M = max |g|,
+// E = frexp exponent of M, K = ceil(log2(16 k^2 H W)), s = 62 - E - K; every contribution v (the fp32 value the atomic path adds) becomes
+// q = rne(v * 2^s) as an int64, the int64 sums are exact and order-free, and each cell gets g = g + (float)((double)Q * 2^-s).  Planes with
+// an inf / NaN take a serial fp32 scatter instead (det_fallback).  Workspace: B*C plane maxima (|g| bits), then B*C planes of
+// Hi x Wi int64 cells.
+struct DetAcc {
+    unsigned long long *acc;   // B*C planes of Hi*Wi int64 cells (two's complement in unsigned words: atomicAdd wraps the same way)
+    const unsigned *pmax;      // B*C plane maxima, as the bits of |g|: >= 0x7f800000 = inf or NaN in the plane
+    int K;
+};
+
+// E and s of a plane from its maximum's bits; false: the plane adds nothing here (all zero, or non-finite: the fallback's)
+__device__ __forceinline__ bool det_scale(unsigned m, int K, int &s)
+{
+    if (m == 0u || m >= 0x7f800000u) return false;
+    const int E = m >= 0x00800000u ? (int)(m >> 23) - 126 : (32 - __clz((int)m)) - 149;   // 2^(E-1) <= M < 2^E, subnormals included
+    s = 62 - E - K;
+    return true;
+}
+// q = round-to-nearest-even(v * 2^s): the scaling is exact in double (s may exceed fp32's exponent range), one rounding to int64
+__device__ __forceinline__ unsigned long long det_q(float v, int s)
+{
+    return (unsigned long long)__double2ll_rn(ldexp((double)v, s));
+}
+__device__ __forceinline__ void det_add(unsigned long long *a, float v, int s) { atomicAdd(a, det_q(v, s)); }
 
 // ---------------------------------------------------------------- forward
 template <int PX>
@@ -133,11 +161,15 @@ __global__ __launch_bounds__(256) void resample_fwd_kernel(const float *__restri
 // One lane per output pixel, lanes along x (coalesced flow / grad_out reads, coalesced grad_flow
 // writes).  grad_img scatter: 4 fp32 hardware atomics per (pixel, channel); neighbouring lanes
 // mostly hit neighbouring addresses, which the memory pipeline merges per cache line.
+// DET: the deterministic mode -- the scatter adds fixed-point contributions to the workspace's int64 planes (DetAcc) instead of
+// fp32 atomics to gimg; the gather is unchanged.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void resample_bwd_kernel(const float *__restrict__ img, ImgStrides is,
                                                            const float *__restrict__ flow,
                                                            const float *__restrict__ gout,
                                                            float *__restrict__ gimg, float *__restrict__ gflow,
-                                                           int C, int Hi, int Wi, int H, int W, long npix)
+                                                           int C, int Hi, int Wi, int H, int W, long npix,
+                                                           DetAcc det = DetAcc{})
 {
     const long HW = (long)H * W, HWi = (long)Hi * Wi;
     for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < npix; g += (long)gridDim.x * blockDim.x) {
@@ -168,11 +200,22 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const float *__restri
 
         for (int ch = 0; ch < C; ++ch) {
             const float go = gout[((long)b * C + ch) * HW + p];
-            float *G = gimg + ((long)b * C + ch) * HWi;
-            unsafeAtomicAdd(G + (long)syT * Wi + sxL, s00 * go);
-            unsafeAtomicAdd(G + (long)syT * Wi + sxR, s01 * go);
-            unsafeAtomicAdd(G + (long)syB * Wi + sxL, s10 * go);
-            unsafeAtomicAdd(G + (long)syB * Wi + sxR, s11 * go);
+            if constexpr (DET) {
+                int ds;
+                if (det_scale(det.pmax[(long)b * C + ch], det.K, ds)) {
+                    unsigned long long *A = det.acc + ((long)b * C + ch) * HWi;
+                    det_add(A + (long)syT * Wi + sxL, s00 * go, ds);
+                    det_add(A + (long)syT * Wi + sxR, s01 * go, ds);
+                    det_add(A + (long)syB * Wi + sxL, s10 * go, ds);
+                    det_add(A + (long)syB * Wi + sxR, s11 * go, ds);
+                }
+            } else {
+                float *G = gimg + ((long)b * C + ch) * HWi;
+                unsafeAtomicAdd(G + (long)syT * Wi + sxL, s00 * go);
+                unsafeAtomicAdd(G + (long)syT * Wi + sxR, s01 * go);
+                unsafeAtomicAdd(G + (long)syB * Wi + sxL, s10 * go);
+                unsafeAtomicAdd(G + (long)syB * Wi + sxR, s11 * go);
+            }
 
             const float *I = img + (long)b * is.b + (long)ch * is.c;
             const float iTL = I[gyT * is.h + gxL * is.w], iTR = I[gyT * is.h + gxR * is.w];
@@ -243,10 +286,12 @@ __global__ __launch_bounds__(256) void resample_fwd_ks_kernel(const float *__res
     }
 }
 
+template <bool DET = false>   // DET: as resample_bwd_kernel
 __global__ __launch_bounds__(256) void resample_bwd_ks_kernel(const float *__restrict__ img, ImgStrides is,
                                                               const float *__restrict__ flow, const float *__restrict__ gout,
                                                               float *__restrict__ gimg, float *__restrict__ gflow,
-                                                              int C, int Hi, int Wi, int H, int W, long npix, int ks)
+                                                              int C, int Hi, int Wi, int H, int W, long npix, int ks,
+                                                              DetAcc det = DetAcc{})
 {
     const long HW = (long)H * W, HWi = (long)Hi * Wi;
     const int span = 2 * ((ks - 1) / 2);   // the flow gradient walks offsets 0 .. 2 * kernel_rad (:171, :184)
@@ -268,14 +313,26 @@ __global__ __launch_bounds__(256) void resample_bwd_ks_kernel(const float *__res
         for (int ch = 0; ch < C; ++ch) {
             const float go = gout[((long)b * C + ch) * HW + p];
             float *G = gimg + ((long)b * C + ch) * HWi;
+            int ds = 0;
+            if constexpr (DET) {
+                if (!det_scale(det.pmax[(long)b * C + ch], det.K, ds)) continue;
+            }
             for (int fy = 0; fy < ks; ++fy)
                 for (int fx = 0; fx < ks; ++fx) {
                     const long yt = (long)clampi(syT + fy, 0, Hi - 1) * Wi, yb = (long)clampi(syB + fy, 0, Hi - 1) * Wi;
                     const int xl = clampi(sxL + fx, 0, Wi - 1), xr = clampi(sxR + fx, 0, Wi - 1);
-                    unsafeAtomicAdd(G + yt + xl, s00 * go);
-                    unsafeAtomicAdd(G + yt + xr, s01 * go);
-                    unsafeAtomicAdd(G + yb + xl, s10 * go);
-                    unsafeAtomicAdd(G + yb + xr, s11 * go);
+                    if constexpr (DET) {
+                        unsigned long long *A = det.acc + ((long)b * C + ch) * HWi;
+                        det_add(A + yt + xl, s00 * go, ds);
+                        det_add(A + yt + xr, s01 * go, ds);
+                        det_add(A + yb + xl, s10 * go, ds);
+                        det_add(A + yb + xr, s11 * go, ds);
+                    } else {
+                        unsafeAtomicAdd(G + yt + xl, s00 * go);
+                        unsafeAtomicAdd(G + yt + xr, s01 * go);
+                        unsafeAtomicAdd(G + yb + xl, s10 * go);
+                        unsafeAtomicAdd(G + yb + xr, s11 * go);
+                    }
                 }
         }
         // grad_flow (:163-192): corners clamped with the flow dims, loops i (x offset), j (y offset), channel
@@ -764,7 +821,8 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
                                                             const float *__restrict__ gout,
                                                             float *__restrict__ gimg, float *__restrict__ gflow,
                                                             int C, int Hi, int Wi, int H, int W, int tiles_x, int tiles_y,
-                                                            int abl)   // abl: profiling switches (0 in production)
+                                                            int abl,   // abl: profiling switches (0 in production)
+                                                            DetAcc det = DetAcc{})   // ACC 2 only
 {
     // Two workgroups per CU (<= 64 VGPRs, 2 x 49 KB LDS): one workgroup's window loads overlap the other's LDS scatter.
     // Per-pixel state is therefore kept small: the four corners are base + {0, dx, dy*stride, both} with dx, dy in {0,1}
@@ -775,7 +833,9 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
     // accumulation window (+1: rows on different banks).  ACC 0: fp32 cells, added to with a compare-and-swap loop (lds_add_f32);
     // ACC 1: fp64 cells, added to with ds_add_f64 -- no return value, no retry loop, no round trip per add (the returning LDS
     // atomic is what bounds the CAS loop, scripts/ubench/lds_cas_pipelined.hip); the sum is rounded to fp32 once, at the flush.
-    typedef std::conditional_t<ACC == 1, double, float> acc_t;
+    // ACC 2: the deterministic mode -- int64 fixed-point cells (same bytes as fp64), ds_add_u64 in LDS, 64-bit integer atomics into the
+    // workspace's accumulator planes for far pixels and the flush; grad_img itself is written by the conversion pass.
+    typedef std::conditional_t<ACC == 2, unsigned long long, std::conditional_t<ACC == 1, double, float>> acc_t;
     __shared__ acc_t awin[WH * WWP];
     enum { LIVE = 1, S_IN = 2, G_IN = 4, S_DX = 8, S_DY = 16, G_DX = 32, G_DY = 64 };
 
@@ -884,6 +944,13 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
     for (int c = 0; c < C; ++c) {
         const float *I = img + (long)b * is.b + (long)c * is.c;
         float *G = gimg + ((long)b * C + c) * HWi;
+        int ds = 0;                 // ACC 2: the plane's scale exponent; dq false = nothing to add for this plane
+        bool dq = true;
+        unsigned long long *A = nullptr;
+        if constexpr (ACC == 2) {
+            dq = det_scale(det.pmax[(long)b * C + c], det.K, ds);
+            A = det.acc + ((long)b * C + c) * HWi;
+        }
         float gov[PPT];   // the channel's grad_out values of the thread: requested together (one round trip, not PPT)
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
@@ -902,10 +969,15 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
             const float go = gov[k];
             const float s00 = (1 - alpha[k]) * (1 - beta[k]), s01 = alpha[k] * (1 - beta[k]);
             const float s10 = (1 - alpha[k]) * beta[k], s11 = alpha[k] * beta[k];
-            if (abl & 2) {
+            if ((abl & 2) || !dq) {
             } else if (fl & S_IN) {
                 const int ox = (fl & S_DX) ? 1 : 0, oy = (fl & S_DY) ? WWP : 0;
-                if constexpr (ACC == 1) {
+                if constexpr (ACC == 2) {
+                    det_add(awin + sb, s00 * go, ds);
+                    det_add(awin + sb + ox, s01 * go, ds);
+                    det_add(awin + sb + oy, s10 * go, ds);
+                    det_add(awin + sb + oy + ox, s11 * go, ds);
+                } else if constexpr (ACC == 1) {
                     lds_add_f64(awin + sb, s00 * go);
                     lds_add_f64(awin + sb + ox, s01 * go);
                     lds_add_f64(awin + sb + oy, s10 * go);
@@ -916,6 +988,12 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
                     lds_add_f32(awin + sb + oy, s10 * go);
                     lds_add_f32(awin + sb + oy + ox, s11 * go);
                 }
+            } else if constexpr (ACC == 2) {
+                const int ox = (fl & S_DX) ? 1 : 0, oy = (fl & S_DY) ? Wi : 0;
+                det_add(A + sb, s00 * go, ds);
+                det_add(A + sb + ox, s01 * go, ds);
+                det_add(A + sb + oy, s10 * go, ds);
+                det_add(A + sb + oy + ox, s11 * go, ds);
             } else {
                 const int ox = (fl & S_DX) ? 1 : 0, oy = (fl & S_DY) ? Wi : 0;
                 unsafeAtomicAdd(G + sb, s00 * go);
@@ -953,7 +1031,10 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
                 const acc_t v = awin[ly * WWP + lx];
                 if (v != (acc_t)0) {
                     awin[ly * WWP + lx] = (acc_t)0;
-                    if (!(abl & 1) && gx >= 0 && gx < Wi && gy >= 0 && gy < Hi) unsafeAtomicAdd(G + gy * Wi + gx, (float)v);
+                    if (!(abl & 1) && gx >= 0 && gx < Wi && gy >= 0 && gy < Hi) {
+                        if constexpr (ACC == 2) atomicAdd(A + gy * Wi + gx, v);
+                        else unsafeAtomicAdd(G + gy * Wi + gx, (float)v);
+                    }
                 }
                 ly += NT / WW; lx += NT % WW;
                 if (lx >= WW) { lx -= WW; ++ly; }
@@ -1321,10 +1402,12 @@ __global__ __launch_bounds__(NT, 8) void resample_bwd_c3x(const C3xArgs p)
 
 // Row N2's backward for shapes the tiled kernel does not take (any C, any size): one lane per pixel, corners from global memory,
 // 4 atomics per (pixel, channel) onto a gradient the host initialised with the concat gradient's slice.
+template <bool DET = false>   // DET: as resample_bwd_kernel (planes b * C + c of H x W cells: the second image's gradient)
 __global__ __launch_bounds__(256) void warp_diff_norm_cat_bwd_kernel(const float *__restrict__ pair, const float *__restrict__ flow,
                                                                      const float *__restrict__ outcat, const float *__restrict__ gcat,
                                                                      float *__restrict__ gpair, float *__restrict__ gflow,
-                                                                     int C, int H, int W, long npix, float inv_div_flow, int norm_only, int bilinear)
+                                                                     int C, int H, int W, long npix, float inv_div_flow, int norm_only, int bilinear,
+                                                                     DetAcc det = DetAcc{})
 {
     // norm_only (models.py:157-161 differentiated): outcat / gcat are the B x 1 x H x W norm and its gradient; the warped image is not
     // stored and is recomputed with the forward's arithmetic; no concat terms
@@ -1365,11 +1448,22 @@ __global__ __launch_bounds__(256) void warp_diff_norm_cat_bwd_kernel(const float
             const float go = norm_only ? 0.0f - gd : gcat[((long)b * CC + 2 * C + c) * HW + pix] - gd;
             if (gpair) {
                 gpair[((long)b * 2 * C + c) * HW + pix] = gcat[((long)b * CC + c) * HW + pix] + gd;
-                float *G = gpair + ((long)b * 2 * C + C + c) * HW;
-                unsafeAtomicAdd(G + yT * W + xL, s00 * go);
-                unsafeAtomicAdd(G + yT * W + xR, s01 * go);
-                unsafeAtomicAdd(G + yB * W + xL, s10 * go);
-                unsafeAtomicAdd(G + yB * W + xR, s11 * go);
+                if constexpr (DET) {
+                    int ds;
+                    if (det_scale(det.pmax[(long)b * C + c], det.K, ds)) {
+                        unsigned long long *A = det.acc + ((long)b * C + c) * HW;
+                        det_add(A + yT * W + xL, s00 * go, ds);
+                        det_add(A + yT * W + xR, s01 * go, ds);
+                        det_add(A + yB * W + xL, s10 * go, ds);
+                        det_add(A + yB * W + xR, s11 * go, ds);
+                    }
+                } else {
+                    float *G = gpair + ((long)b * 2 * C + C + c) * HW;
+                    unsafeAtomicAdd(G + yT * W + xL, s00 * go);
+                    unsafeAtomicAdd(G + yT * W + xR, s01 * go);
+                    unsafeAtomicAdd(G + yB * W + xL, s10 * go);
+                    unsafeAtomicAdd(G + yB * W + xR, s11 * go);
+                }
             }
             const float iTL = I[yT * W + xL], iTR = I[yT * W + xR], iBL = I[yB * W + xL], iBR = I[yB * W + xR];
             out_dy = out_dy + (gam_y * go) * iBL;
@@ -1384,6 +1478,112 @@ __global__ __launch_bounds__(256) void warp_diff_norm_cat_bwd_kernel(const float
         if (norm_only) { gflow[(long)b * 2 * HW + pix] = out_dx; gflow[(long)b * 2 * HW + HW + pix] = out_dy; continue; }
         gflow[(long)b * 2 * HW + pix] = out_dx + gcat[((long)b * CC + 3 * C) * HW + pix] * inv_div_flow;
         gflow[(long)b * 2 * HW + HW + pix] = out_dy + gcat[((long)b * CC + 3 * C + 1) * HW + pix] * inv_div_flow;
+    }
+}
+
+// ---------------------------------------------------------------- deterministic grad_input1: prepass, fallback, conversion
+// MODE 0: the scattered gradient is grad_out (B x C x H x W); MODE 1: it is warp_diff_norm_cat's g_warped, formed from the concat gradient
+// with the fused kernels' arithmetic (warp_diff_norm_cat_bwd_kernel, c3x_load_go).
+struct DetSrc {
+    const float *gout;                          // MODE 0
+    const float *gcat, *pair, *outcat;          // MODE 1
+    int C;
+    long HW;
+};
+template <int MODE>
+__device__ __forceinline__ float det_src(const DetSrc &d, int b, int c, long pix)
+{
+    if constexpr (MODE == 0) return d.gout[((long)b * d.C + c) * d.HW + pix];
+    const long CC = 3L * d.C + 3;
+    const float gn = d.gcat[((long)b * CC + 3 * d.C + 2) * d.HW + pix], nrm = d.outcat[((long)b * CC + 3 * d.C + 2) * d.HW + pix];
+    const float diff = d.pair[((long)b * 2 * d.C + c) * d.HW + pix] - d.outcat[((long)b * CC + 2 * d.C + c) * d.HW + pix];
+    return d.gcat[((long)b * CC + 2 * d.C + c) * d.HW + pix] - chnorm_grad(gn, diff, nrm);
+}
+
+// max |g| per plane as the bits of |g| (their integer order is the order of the magnitudes, NaN above inf): one integer atomicMax per
+// workgroup, whatever order the workgroups arrive in.  A workgroup takes DET_MAX_PER x 256 consecutive values of one plane, its loads all
+// in flight at once.  Grid: planes x chunks, chunk = blockIdx.x % chunks.
+constexpr int DET_MAX_PER = 16;
+template <int MODE>
+__global__ __launch_bounds__(256) void det_plane_max_kernel(const DetSrc d, unsigned *__restrict__ pmax, int chunks)
+{
+    __shared__ unsigned wmax[4];
+    const long plane = blockIdx.x / chunks;
+    const int b = (int)(plane / d.C), c = (int)(plane % d.C);
+    const long i0 = (long)(blockIdx.x % chunks) * (256L * DET_MAX_PER) + threadIdx.x;
+    float v[DET_MAX_PER];
+    if ((long)(blockIdx.x % chunks + 1) * (256L * DET_MAX_PER) <= d.HW) {   // a whole chunk: unconditional loads, all issued before any use
+#pragma unroll
+        for (int j = 0; j < DET_MAX_PER; ++j) v[j] = det_src<MODE>(d, b, c, i0 + 256L * j);
+    } else {
+#pragma unroll
+        for (int j = 0; j < DET_MAX_PER; ++j) v[j] = i0 + 256L * j < d.HW ? det_src<MODE>(d, b, c, i0 + 256L * j) : 0.0f;
+    }
+    unsigned m = 0u;
+#pragma unroll
+    for (int j = 0; j < DET_MAX_PER; ++j) m = max(m, __float_as_uint(v[j]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+        if (m != 0u) atomicMax(pmax + plane, m);
+    }
+}
+
+// Planes with an inf or a NaN: the oracle's serial fp32 scatter (y, x, window offsets, corners TL TR BL BR) straight into the
+// gradient, one lane per plane (lanes of finite planes return at once).  `G0`: plane (b, c) starts at G0 + b * g_bs + c * Hi * Wi.
+template <int MODE>
+__device__ void det_fallback(const DetSrc &d, const float *__restrict__ flow, const unsigned *__restrict__ pmax, float *__restrict__ G0,
+                             long g_bs, int B, int Hi, int Wi, int H, int W, int ks, long plane)
+{
+    if (plane >= (long)B * d.C || pmax[plane] < 0x7f800000u) return;
+    const int b = (int)(plane / d.C), c = (int)(plane % d.C);
+    const long HW = (long)H * W;
+    float *G = G0 + (long)b * g_bs + (long)c * Hi * Wi;
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const long p = (long)y * W + x;
+            const float xf = (float)x + flow[(long)b * 2 * HW + p], yf = (float)y + flow[(long)b * 2 * HW + HW + p];
+            const float alpha = xf - (float)f2i_sat(xf), beta = yf - (float)f2i_sat(yf);
+            const float fx = floorf(xf), fy = floorf(yf);
+            const int xL = clampi(f2i_sat(fx), 0, Wi - 1), xR = clampi(f2i_sat(fx + 1.0f), 0, Wi - 1);
+            const int yT = clampi(f2i_sat(fy), 0, Hi - 1), yB = clampi(f2i_sat(fy + 1.0f), 0, Hi - 1);
+            const float go = det_src<MODE>(d, b, c, p);
+            const float s00 = (1 - alpha) * (1 - beta), s01 = alpha * (1 - beta), s10 = (1 - alpha) * beta, s11 = alpha * beta;
+            for (int ky = 0; ky < ks; ++ky)
+                for (int kx = 0; kx < ks; ++kx) {
+                    const long yt = (long)clampi(yT + ky, 0, Hi - 1) * Wi, yb = (long)clampi(yB + ky, 0, Hi - 1) * Wi;
+                    const int xl = clampi(xL + kx, 0, Wi - 1), xr = clampi(xR + kx, 0, Wi - 1);
+                    G[yt + xl] = G[yt + xl] + s00 * go;
+                    G[yt + xr] = G[yt + xr] + s01 * go;
+                    G[yb + xl] = G[yb + xl] + s10 * go;
+                    G[yb + xr] = G[yb + xr] + s11 * go;
+                }
+        }
+}
+
+// Step 5 of the contract: r = (float)((double)Q * 2^-s) -- int64 -> double and double -> float, both round-to-nearest-even, subnormals
+// kept -- and one fp32 add into the gradient.  Planes that add nothing (all zero, or non-finite) are left untouched here: the last
+// `gridDim.x - ncvt` workgroups run the serial fallback of the non-finite ones, one lane per plane (disjoint cells, no ordering needed).
+template <int MODE>
+__global__ __launch_bounds__(256) void det_convert_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ pmax, int K,
+                                                          float *__restrict__ G0, long g_bs, int C, long HWi, long ncell, unsigned ncvt,
+                                                          const DetSrc d, const float *__restrict__ flow, int B, int Hi, int Wi, int H, int W,
+                                                          int ks)
+{
+    if (blockIdx.x >= ncvt) {
+        det_fallback<MODE>(d, flow, pmax, G0, g_bs, B, Hi, Wi, H, W, ks, (long)(blockIdx.x - ncvt) * blockDim.x + threadIdx.x);
+        return;
+    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < ncell; i += (long)ncvt * blockDim.x) {
+        const long plane = i / HWi, cell = i - plane * HWi;
+        int s;
+        if (!det_scale(pmax[plane], K, s)) continue;
+        const float r = __double2float_rn(ldexp(__ll2double_rn((long long)acc[i]), -s));
+        float *g = G0 + (plane / C) * g_bs + (plane % C) * HWi + cell;
+        *g = *g + r;
     }
 }
 
@@ -1599,7 +1799,7 @@ static int resample2d_backward_impl(const float *img, const int64_t *img_strides
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long npix = (long)B * H * W;
     if (kernel_size != 1) {
-        hipLaunchKernelGGL(resample_bwd_ks_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
+        hipLaunchKernelGGL(resample_bwd_ks_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
                            grad_flow, C, Hi, Wi, H, W, npix, kernel_size);
         return launch_status();
     }
@@ -1643,7 +1843,7 @@ static int resample2d_backward_impl(const float *img, const int64_t *img_strides
         }
 #undef FN2_RB
     } else {
-        hipLaunchKernelGGL(resample_bwd_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out,
+        hipLaunchKernelGGL(resample_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out,
                            grad_img, grad_flow, C, Hi, Wi, H, W, npix);
     }
     return launch_status();
@@ -1740,7 +1940,7 @@ extern "C" int fn2_warp_diff_norm_cat_backward(const float *pair, const float *f
         else hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, 1, false>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
         return launch_status();
     }
-    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_cat, grad_cat, grad_pair,
+    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_cat, grad_cat, grad_pair,
                        grad_flow, C, H, W, npix, inv, 0, 1);
     return launch_status();
 }
@@ -1799,7 +1999,146 @@ extern "C" int fn2_warp_diff_norm_backward(const float *pair, const float *flow,
         hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, 2, false>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
         return launch_status();
     }
-    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, norm, grad_norm,
+    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, norm, grad_norm,
                        static_cast<float *>(nullptr), grad_flow, C, H, W, npix, 0.0f, 1, bilinear);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------- deterministic backward (fixed-point grad_input1)
+// Workspace: the plane maxima (4 B per plane, rounded up to 256 B), then B*C planes of Hi x Wi int64 accumulators.
+static size_t det_workspace_bytes(long planes, long HWi)
+{
+    return (size_t)((4 * planes + 255) / 256 * 256) + (size_t)(8 * planes * HWi);
+}
+// K of the contract: the smallest K with 2^K >= 16 k^2 H W
+static int det_K(int ks, int H, int W)
+{
+    const unsigned long long n = 16ull * (unsigned long long)ks * ks * (unsigned long long)H * W;
+    int K = 0;
+    while (K < 63 && (1ull << K) < n) ++K;
+    return K;
+}
+
+// clear the workspace and find the plane maxima (the first two steps of every deterministic call)
+template <int MODE>
+static int det_begin(const fn2::DetSrc &d, int B, void *workspace, size_t bytes, fn2::DetAcc &det, int K, hipStream_t s)
+{
+    using namespace fn2;
+    const long planes = (long)B * d.C;
+    hipError_t e = hipMemsetAsync(workspace, 0, bytes, s);
+    if (e != hipSuccess) return (int)e;
+    det.pmax = static_cast<unsigned *>(workspace);
+    det.acc = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + (4 * planes + 255) / 256 * 256);
+    det.K = K;
+    if (planes > 0) {
+        const int chunks = (int)((d.HW + 256L * DET_MAX_PER - 1) / (256L * DET_MAX_PER));
+        hipLaunchKernelGGL(det_plane_max_kernel<MODE>, dim3((unsigned)(planes * chunks)), dim3(256), 0, s, d,
+                           static_cast<unsigned *>(workspace), chunks);
+    }
+    return launch_status();
+}
+
+// the conversion of the finite planes and the serial scatter of the non-finite ones, in one launch
+template <int MODE>
+static void det_end(const fn2::DetSrc &d, const float *flow, const fn2::DetAcc &det, float *G0, long g_bs, int B, int Hi, int Wi, int H,
+                    int W, int ks, hipStream_t s)
+{
+    using namespace fn2;
+    const long planes = (long)B * d.C, HWi = (long)Hi * Wi;
+    if (planes == 0) return;
+    const unsigned ncvt = stream_grid(planes * HWi), nfb = (unsigned)((planes + 255) / 256);
+    hipLaunchKernelGGL(det_convert_kernel<MODE>, dim3(ncvt + nfb), dim3(256), 0, s, det.acc, det.pmax, det.K, G0, g_bs, d.C, HWi, planes * HWi,
+                       ncvt, d, flow, B, Hi, Wi, H, W, ks);
+}
+
+extern "C" size_t fn2_resample2d_backward_det_workspace_bytes(int B, int C, int Hi, int Wi, int H, int W, int kernel_size)
+{
+    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0 || kernel_size < 1) return 0;
+    return det_workspace_bytes((long)B * C, (long)Hi * Wi);
+}
+
+extern "C" int fn2_resample2d_backward_det(const float *img, const int64_t *img_strides, const float *flow,
+                                           const float *grad_out, float *grad_img, float *grad_flow,
+                                           int B, int C, int Hi, int Wi, int H, int W,
+                                           int kernel_size, int bilinear, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace fn2;
+    (void)bilinear;   // both reference backward kernels ignore the flag
+    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0) return FN2_EINVAL;
+    if (kernel_size < 1) return FN2_EINVAL;
+    if ((long)B * H * W == 0) return FN2_OK;
+    if (!img || !flow || !grad_out || !grad_img || !grad_flow) return FN2_EINVAL;
+    const size_t need = det_workspace_bytes((long)B * C, (long)Hi * Wi);
+    if (!workspace || workspace_bytes < need) return FN2_EINVAL;
+    if (!aligned(img, 4) || !aligned(flow, 4) || !aligned(grad_out, 4) || !aligned(grad_img, 4) || !aligned(grad_flow, 4) ||
+        !aligned(workspace, 8))
+        return FN2_EALIGN;
+    ImgStrides is;
+    if (img_strides) { is.b = img_strides[0]; is.c = img_strides[1]; is.h = img_strides[2]; is.w = img_strides[3]; }
+    else { is.b = (long)C * Hi * Wi; is.c = (long)Hi * Wi; is.h = Wi; is.w = 1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long npix = (long)B * H * W;
+    DetSrc d{};
+    d.gout = grad_out; d.C = C; d.HW = (long)H * W;
+    DetAcc det{};
+    int rc = det_begin<0>(d, B, workspace, need, det, det_K(kernel_size, H, W), s);
+    if (rc != FN2_OK) return rc;
+    // the atomic path's kernels with the scatter turned into fixed-point adds (same gather, same grad_flow); the tiled shapes take the
+    // per-channel LDS-window kernel for every C, its window cells int64 instead of fp64
+    const bool tiled_ok = (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && aligned(img, 16) &&
+                          (Hi == H) && (Wi == W) && (W % 4 == 0) && (H >= 16) && (W >= 32);
+    if (kernel_size != 1) {
+        hipLaunchKernelGGL(resample_bwd_ks_kernel<true>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
+                           grad_flow, C, Hi, Wi, H, W, npix, kernel_size, det);
+    } else if (tiled_ok) {
+        const int tiles_x = (W + 63) / 64, tiles_y = (H + 31) / 32;
+        hipLaunchKernelGGL((resample_bwd_tiled<32, 64, 16, 1024, 8, 2>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), 0, s,
+                           img, is, flow, grad_out, grad_img, grad_flow, C, Hi, Wi, H, W, tiles_x, tiles_y, 0, det);
+    } else {
+        hipLaunchKernelGGL(resample_bwd_kernel<true>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
+                           grad_flow, C, Hi, Wi, H, W, npix, det);
+    }
+    det_end<0>(d, flow, det, grad_img, (long)C * Hi * Wi, B, Hi, Wi, H, W, kernel_size, s);
+    return launch_status();
+}
+
+extern "C" size_t fn2_warp_diff_norm_cat_backward_det_workspace_bytes(int B, int C, int H, int W)
+{
+    if (B < 0 || C < 1 || H < 1 || W < 1) return 0;
+    return det_workspace_bytes((long)B * C, (long)H * W);
+}
+
+extern "C" int fn2_warp_diff_norm_cat_backward_det(const float *pair, const float *flow, const float *out_cat, const float *grad_cat,
+                                                   float *grad_pair, float *grad_flow, float div_flow, int B, int C, int H, int W,
+                                                   int bilinear, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace fn2;
+    if (B < 0 || C < 1 || H < 1 || W < 1 || !(div_flow == div_flow) || div_flow == 0.0f) return FN2_EINVAL;
+    if ((long)B * H * W == 0) return FN2_OK;
+    if (!pair || !flow || !out_cat || !grad_cat || !grad_flow) return FN2_EINVAL;
+    const size_t need = det_workspace_bytes((long)B * C, (long)H * W);
+    if (!workspace || workspace_bytes < need) return FN2_EINVAL;
+    if (!aligned(workspace, 8)) return FN2_EALIGN;
+    // no pair gradient: nothing is scattered, the existing entry point is already deterministic
+    if (!grad_pair) return fn2_warp_diff_norm_cat_backward(pair, flow, out_cat, grad_cat, nullptr, grad_flow, div_flow, B, C, H, W, bilinear, stream);
+    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(out_cat, 4) || !aligned(grad_cat, 4) || !aligned(grad_flow, 4) ||
+        !aligned(grad_pair, 4))
+        return FN2_EALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long HW = (long)H * W, npix = (long)B * HW;
+    // the second image's gradient starts as its slice of the concat gradient, as on the atomic path
+    hipError_t e = hipMemcpy2DAsync(grad_pair + (long)C * HW, 2 * C * HW * sizeof(float), grad_cat + (long)C * HW,
+                                    (3 * C + 3) * HW * sizeof(float), C * HW * sizeof(float), B, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return (int)e;
+    DetSrc d{};
+    d.gcat = grad_cat; d.pair = pair; d.outcat = out_cat; d.C = C; d.HW = HW;
+    DetAcc det{};
+    int rc = det_begin<1>(d, B, workspace, need, det, det_K(1, H, W), s);
+    if (rc != FN2_OK) return rc;
+    // one lane per pixel for every shape: the first image's gradient, the gather of grad_flow and the fixed-point scatter (the arithmetic of
+    // the tiled kernel, resample_bwd_c3x<..., 1, true>: same bits for grad_flow and grad_pair[:, :C])
+    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<true>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_cat, grad_cat, grad_pair,
+                       grad_flow, C, H, W, npix, 1.0f / div_flow, 0, 1, det);
+    det_end<1>(d, flow, det, grad_pair + (long)C * HW, 2L * C * HW, B, H, W, H, W, 1, s);
     return launch_status();
 }

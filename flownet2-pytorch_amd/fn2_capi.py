@@ -23,6 +23,8 @@ EXPORTS = [
     "fn2_channelnorm_forward", "fn2_channelnorm_backward",
     "fn2_multiscale_workspace_bytes", "fn2_multiscale_l1_epe", "fn2_multiscale_loss",
     "fn2_multiscale_loss_fused", "fn2_multiscale_scale_grads",
+    "fn2_resample2d_backward_det_workspace_bytes", "fn2_resample2d_backward_det",
+    "fn2_warp_diff_norm_cat_backward_det_workspace_bytes", "fn2_warp_diff_norm_cat_backward_det",
 ]
 
 # profiling / ablation entry points (csrc/fn2_debug.h): not in include/flownet2_hip.h, results wrong by design; exported by
@@ -51,6 +53,8 @@ def lib():
             getattr(_lib, name).restype = ctypes.c_int
         _lib.fn2_multiscale_workspace_bytes.restype = ctypes.c_size_t
         _lib.fn2_correlation_backward_fused_workspace_bytes.restype = ctypes.c_size_t
+        _lib.fn2_resample2d_backward_det_workspace_bytes.restype = ctypes.c_size_t
+        _lib.fn2_warp_diff_norm_cat_backward_det_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 
 

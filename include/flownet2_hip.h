@@ -247,6 +247,46 @@ int fn2_warp_diff_norm_cat_backward(const float *pair, const float *flow, const 
                                     float *grad_pair, float *grad_flow, float div_flow, int B, int C, int H, int W,
                                     int bilinear, void *stream);
 
+/* Deterministic backward: fn2_resample2d_backward and fn2_warp_diff_norm_cat_backward with the image gradient summed in fixed point,
+ * so that it has the same bits whatever order the contributions arrive in (run to run, stream to stream, any batch split).  Added
+ * without an ABI version change (FN2_ABI_VERSION stays 3): a caller detects these entry points by looking up their symbols, as bf16
+ * support is detected without a version change.
+ *
+ * Contract, per plane (b, c) of the gradient being scattered (grad_out; for warp_diff_norm_cat g_warped = grad_cat[:, 2C:3C] - g_diff,
+ * formed with the fused kernel's arithmetic):
+ *  1. M = max |g| over the plane's H x W values.  M inf or NaN: the plane takes step 6.  M == 0: the plane adds nothing.
+ *  2. E: 2^(E-1) <= M < 2^E (frexpf's exponent, subnormal M included).  K: the smallest integer with 2^K >= 16 k^2 H W
+ *     (k = kernel_size).  s = 62 - E - K.  The scatter weights use truncation (alpha = xf - (int)xf), so |weight| < 4, and one source
+ *     pixel adds at most 4 k^2 contributions to one cell (clamping piles corners onto one cell): |sum of a cell| < 2^(E+K), the int64
+ *     sums cannot overflow.
+ *  3. Each contribution v is the fp32 value the atomic path adds: ((1 - alpha) * (1 - beta)) * g and its three siblings, evaluated in
+ *     fp32, left to right, no contraction.
+ *  4. q = round-to-nearest-even(v * 2^s) as an int64, the scaling done in double (exact).
+ *  5. Q = sum of q per cell (exact: any order).  r = (float)((double)Q * 2^-s): int64 -> double, then double -> float, both
+ *     round-to-nearest-even, subnormals kept.  grad_img[cell] = grad_img[cell] + r (one fp32 add: accumulate-into, as the atomic
+ *     path; cells of planes with M == 0 are not touched).
+ *  6. A plane whose M is inf or NaN is scattered serially in the oracle's order -- y, x, window offsets, corners TL TR BL BR -- with
+ *     fp32 adds straight into grad_img: deterministic, and equal to the serial reference scatter when grad_img starts at zero.  It
+ *     does not affect the other planes.
+ * Error bound: each contribution is quantised with an error of at most 2^(E+K-63); a cell's r differs from the exact sum of its
+ * contributions by at most (number of contributions) * 2^(E+K-63), plus 2^-53 relative (int64 -> double) and one fp32 rounding.  The result of batch item b does not depend
+ * on the other items.  grad_flow (a gather) is what the atomic entry point writes, bit for bit.
+ *
+ *   workspace       : device scratch of at least *_det_workspace_bytes(...) bytes, 8-byte aligned, contents irrelevant (it is
+ *                     cleared on the stream first); B*C plane maxima (rounded up to 256 bytes) + B*C*Hi*Wi int64 accumulators
+ *   workspace_bytes : its size; NULL or too small -> FN2_EINVAL before anything is launched
+ * Other arguments, shapes and rejected calls as the atomic entry points.  The workspace-size functions return 0 for invalid shapes.
+ * fn2_warp_diff_norm_cat_backward_det with grad_pair == NULL scatters nothing and is fn2_warp_diff_norm_cat_backward. */
+size_t fn2_resample2d_backward_det_workspace_bytes(int B, int C, int Hi, int Wi, int H, int W, int kernel_size);
+int fn2_resample2d_backward_det(const float *img, const int64_t *img_strides, const float *flow,
+                                const float *grad_out, float *grad_img, float *grad_flow,
+                                int B, int C, int Hi, int Wi, int H, int W,
+                                int kernel_size, int bilinear, void *workspace, size_t workspace_bytes, void *stream);
+size_t fn2_warp_diff_norm_cat_backward_det_workspace_bytes(int B, int C, int H, int W);
+int fn2_warp_diff_norm_cat_backward_det(const float *pair, const float *flow, const float *out_cat, const float *grad_cat,
+                                        float *grad_pair, float *grad_flow, float div_flow, int B, int C, int H, int W,
+                                        int bilinear, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Row N2 without the concat -- the other two warp sites of FlowNet2 (models.py:157-161, :170-174):
  *   out_norm = ChannelNorm(pair[:, :C] - Resample2d(pair[:, C:], flow))      B x 1 x H x W, fully written
  * by the kernel of fn2_warp_diff_norm_cat storing only the norm plane (bit-identical to that plane), and its backward with respect
