@@ -20,9 +20,14 @@ BASELINE.json's metric names): achieved = algorithmic bytes of one launch (SURVE
 2*B*C*H*W*4 read + B*441*H*W*4 written = 93 683 712 B) / mean launch duration, measured with HIP
 events on the launch stream inside the timed steps (an event pair around that kernel in every fourth timed step, on
 events created before the region; the other five ops are timed in a second pass over the same K steps: event pairs
-around everything cost 10-25 % of a 0.19 ms step, host-dependent).  `cpu_baseline` times the CPU oracle
-(oracle/, a restatement of the reference kernels; the reference itself has no CPU path) on a
-bounded sample of the same workload on the host cores.
+around everything cost 10-25 % of a 0.19 ms step, host-dependent).
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs and
+the line.  `--full` adds, after the timed steps, everything that takes runs of its own: per-rank probes, the
+per-kernel second pass (`kernels`), the autograd-module steps, the graded kernel's fabric traffic and the copy /
+matrix ceilings beside `roofline`, probes of the box, `cpu_baseline` (the CPU oracle -- oracle/, a restatement of
+the reference kernels; the reference itself has no CPU path -- on a bounded sample of the same workload on the
+host cores) with `cpu_baseline_fast`, and the whole FlowNet2C network (`flownet2c`).
 """
 import argparse
 import json
@@ -677,7 +682,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: per-rank probes, per-kernel "
+                         "times and the roofline's ceilings, the autograd-module steps, the graded kernel's fabric traffic, probes of "
+                         "the box, the CPU baselines and the FlowNet2C network.  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--graph", nargs="?", const="on", default="auto", choices=("auto", "on", "off"),
                     help="replay a hipGraph of the step instead of launching it eagerly; auto = eager at one GPU (the documented "
                          "headline), graph replay for --gpus N > 1: one launch per step, so that a noisy host core cannot make a "
@@ -685,12 +695,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-fast-seconds", type=float, default=12.0)
     ap.add_argument("--model", choices=("auto", "on", "off"), default="auto",
-                    help="also time the whole FlowNet2C network around the layers (extra key `flownet2c`; never `value`); auto = on "
-                         "for one GPU, off for --gpus N > 1 (N ranks each running MIOpen's kernel search under the watchdog is how a "
-                         "scaling run ends with a truncated line)")
+                    help="with --full: also time the whole FlowNet2C network around the layers (extra key `flownet2c`; never `value`); "
+                         "auto = on for one GPU, off for --gpus N > 1 (N ranks each running MIOpen's kernel search under the watchdog "
+                         "is how a scaling run ends with a truncated line)")
     ap.add_argument("--pmc", choices=("auto", "on", "off"), default="auto",
-                    help="measure the graded kernel's fabric traffic in THIS run (two rocprofv3 --pmc passes over a tiny child "
-                         "process, one GPU only); auto = on where rocprofv3 is installed")
+                    help="with --full: measure the graded kernel's fabric traffic in THIS run (two rocprofv3 --pmc passes over a tiny "
+                         "child process, one GPU only); auto = on where rocprofv3 is installed")
     ap.add_argument("--placement", choices=("auto", "on", "off"), default="auto",
                     help="untimed set-up: re-place the step's buffers when the step is > 10 %% above the sum of its kernels (auto), always try (on), never (off)")
     ap.add_argument("--model-steps", type=int, default=20)
@@ -702,6 +712,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    for opt in ("model", "pmc"):
+        if getattr(args, opt) == "on" and not args.full:
+            ap.error(f"--{opt} on measures beside the headline: it needs --full")
 
     import dist_utils
     assert torch.cuda.is_available(), "bench.py needs a GPU: the HIP kernels are the only implementation"
@@ -824,8 +837,8 @@ def main():
     dumped = hp.dump_outputs(args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # per-rank consistency check: every rank's own time for its K steps and a checksum of its results
     chk = float(hp.out.double().sum().item() + hp.g1.double().sum().item() + hp.norm.double().sum().item())
-    # two probes of THIS rank's GPU, so that an N-GPU line explains itself (the step time is the slowest rank's): the graded kernel
-    # alone, back to back (operands cache-resident), and a 256 MiB device copy
+    # --full: two probes of THIS rank's GPU, so that an N-GPU line explains itself (the step time is the slowest rank's): the graded
+    # kernel alone, back to back (operands cache-resident), and a 256 MiB device copy
     def rank_probes():
         ts = []
         for _ in range(9):
@@ -840,7 +853,7 @@ def main():
             s_.record(); b_.copy_(a_); e_.record(); torch.cuda.synchronize()
             cs.append(s_.elapsed_time(e_))
         return sorted(ts)[len(ts) // 2], 2 * a_.numel() * 4 / (min(cs) * 1e-3) / 1e9
-    probe_us, probe_copy = rank_probes()
+    probe_us, probe_copy = rank_probes() if args.full else (float("nan"), float("nan"))
     mine = torch.tensor([own_elapsed, chk, float(torch.cuda.current_device()), probe_us, probe_copy], dtype=torch.float64, device=dev)
     if dist is not None:
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -849,7 +862,7 @@ def main():
         allr = [mine]
     per_rank = [{"rank": r, "device": int(t[2].item()), "ms_per_step": round(float(t[0].item()) / args.steps * 1e3, 4),
                  "image_pairs_per_s": round(CORR["B"] * args.steps / float(t[0].item()), 1),
-                 "corr_fwd_us_warm": round(float(t[3].item()), 1), "copy_GBps_torch": round(float(t[4].item()), 1),
+                 **({"corr_fwd_us_warm": round(float(t[3].item()), 1), "copy_GBps_torch": round(float(t[4].item()), 1)} if args.full else {}),
                  "finite": bool(torch.isfinite(t[1]).item())} for r, t in enumerate(allr)]
     # where each rank ran: the GPU's slot (PCI bus id, NUMA node, XGMI hive) and the host cores the rank pinned itself to
     ident = dict(gpu_identity(torch.cuda.current_device()), cpu_cores=(f"{pinned[0]}-{pinned[-1]} ({len(pinned)})" if pinned else None),
@@ -865,19 +878,20 @@ def main():
     # efficiency relative to N copies of its own fastest rank (the driver computes efficiency across runs from `value` itself)
     rank_balance = round(min(float(t[0].item()) for t in allr) / max(float(t[0].item()) for t in allr), 4)
 
-    # Per-kernel durations: the same K steps once more with a HIP event pair around every op on the launch stream
-    # (same kernels, same inputs; rocprofv3's per-kernel averages of this command agree).
     events = {}
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        hp.step(events)
-    torch.cuda.synchronize()
-    eager_elapsed = time.perf_counter() - t1
+    if args.full:
+        # Per-kernel durations: the same K steps once more with a HIP event pair around every op on the launch stream
+        # (same kernels, same inputs; rocprofv3's per-kernel averages of this command agree).
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            hp.step(events)
+        torch.cuda.synchronize()
+        eager_elapsed = time.perf_counter() - t1
 
-    # The same step through the shipped autograd wrappers (Correlation / Resample2d / ChannelNorm modules, with the
-    # difference op of models.py:135 between warp and norm): what a training script pays, allocations included.
-    mod_elapsed, mod_fused_elapsed, mod_same_elapsed, mod_floor_elapsed = hp.module_steps(args.steps)
+        # The same step through the shipped autograd wrappers (Correlation / Resample2d / ChannelNorm modules, with the
+        # difference op of models.py:135 between warp and norm): what a training script pays, allocations included.
+        mod_elapsed, mod_fused_elapsed, mod_same_elapsed, mod_floor_elapsed = hp.module_steps(args.steps)
 
     if rank == 0:
         per_op_ms = {k: sum(s.elapsed_time(e) for s, e in v) / len(v) for k, v in events.items()}
@@ -889,6 +903,51 @@ def main():
                        "achieved_GBps": round(ab[k] / (ms * 1e-3) / 1e9, 2),
                        "frac_of_8TBps": round(ab[k] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
                    for k, ms in per_op_ms.items()}
+        pairs = CORR["B"] * args.steps * world
+        line = {
+            "metric": "image-pairs/sec, FlowNet2 custom-layer hot path (Correlation + Resample2d + ChannelNorm) fwd+bwd @ 384x512 "
+                      "bs8 -- the whole FlowNet2C network's fwd+bwd image-pairs/sec is flownet2c.fwd_bwd_image_pairs_per_s; "
+                      "corr-layer HBM GB/s vs roofline is `roofline`",
+            "value": round(pairs / elapsed, 3),
+            "unit": "image-pairs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "launch": "hipGraph replay of the step" if graph is not None else "eager launches",
+            "placement_autotune": placement,   # untimed set-up: step time per buffer placement tried, the one the timed steps ran with
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "full": args.full,   # False: no figure that takes runs of its own (per-kernel, ceilings, CPU, FlowNet2C) is in the line
+            "config": {
+                "workload": "FlowNet2 custom-layer hot path fwd+bwd, bs8 @384x512: Correlation 8x256x48x64 "
+                            "(20,1,20,1,2) [BASELINE configs[1]] + Resample2d 8x3x384x512 + ChannelNorm 8x3x384x512",
+                "pairs_per_step_per_gpu": CORR["B"],
+                "sharding": "batch over ranks, no data-path collective",
+            },
+            "per_rank": per_rank,
+            "rank_balance_fastest_over_slowest": rank_balance,
+        }
+        # the graded kernel against the HBM roof from the event pairs inside the timed region (eager launches; under graph replay
+        # only --full's second pass times it); the ceilings and the traffic beside it take runs of their own and come with --full
+        if "corr_fwd" in kernels:
+            cf = kernels["corr_fwd"]
+            line["roofline"] = {"kernel": "correlation forward (corr_fwd_f16x2)", "bound": "hbm", "achieved": cf["achieved_GBps"],
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(cf["achieved_GBps"] / HBM_PEAK_GBS, 4),
+                                "launch_ms": cf["ms"], "algorithmic_bytes": cf["algorithmic_bytes"]}
+        assert len(per_rank) == world and all(r["finite"] for r in per_rank), per_rank
+        if share:
+            line["dry_run_shared_gpu"] = True
+        if dumped is not None:
+            line["dump_outputs"] = dumped
+    else:
+        line = None
+
+    # --full: everything beside the headline that takes runs of its own
+    if rank == 0 and args.full:
         cf = kernels["corr_fwd"]
         # HBM-side traffic of the graded kernel: NOT measured in this process (PMC counters need their own rocprofv3 --pmc
         # passes, scripts/gpu_traffic.sh); the tracked result of those passes is quoted with its source
@@ -916,7 +975,6 @@ def main():
             s_.record(); tiny.zero_(); e_.record()
         torch.cuda.synchronize()
         event_floor_ms = sorted(s_.elapsed_time(e_) for s_, e_ in nev)[len(nev) // 2]
-        pairs = CORR["B"] * args.steps * world
         # empirical streaming ceiling of this box: device-to-device copy of 1 GiB, read + write bytes -- a float4
         # grid-stride kernel (fn2_debug_stream_copy in the debug library; the guide quotes 6.29 TB/s for such a copy), best of a
         # few grid sizes and of temporal / non-temporal accesses; torch's copy_ for comparison
@@ -999,18 +1057,7 @@ def main():
             return round(sorted(ts)[len(ts) // 2], 1)
         cold = {"corr_fwd_us_warm": corr_us(False), "corr_fwd_us_after_1GiB_fill": corr_us(True)}
         del junk
-        line = {
-            "metric": "image-pairs/sec, FlowNet2 custom-layer hot path (Correlation + Resample2d + ChannelNorm) fwd+bwd @ 384x512 "
-                      "bs8 -- the whole FlowNet2C network's fwd+bwd image-pairs/sec is flownet2c.fwd_bwd_image_pairs_per_s; "
-                      "corr-layer HBM GB/s vs roofline is `roofline`",
-            "value": round(pairs / elapsed, 3),
-            "unit": "image-pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "launch": "hipGraph replay of the step" if graph is not None else "eager launches",
-            "placement_autotune": placement,   # untimed set-up: step time per buffer placement tried, the one the timed steps ran with
+        line.update({
             "ms_per_step_eager_with_events": round(eager_elapsed / args.steps * 1e3, 4),
             "ms_per_step_autograd_modules": round(mod_elapsed / args.steps * 1e3, 4),
             "ms_per_step_autograd_fused_rows": round(mod_fused_elapsed / args.steps * 1e3, 4),   # Correlation + WarpDiffNorm (flow gradient only)
@@ -1018,40 +1065,9 @@ def main():
             "ms_per_step_autograd_modules_same_kernels": round(mod_same_elapsed / args.steps * 1e3, 4),
             # ... and what two .backward() calls of trivial graphs cost on this host (no kernels to speak of): the floor under both
             "ms_per_step_autograd_host_floor": round(mod_floor_elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "FlowNet2 custom-layer hot path fwd+bwd, bs8 @384x512: Correlation 8x256x48x64 "
-                            "(20,1,20,1,2) [BASELINE configs[1]] + Resample2d 8x3x384x512 + ChannelNorm 8x3x384x512",
-                "pairs_per_step_per_gpu": CORR["B"],
-                "sharding": "batch over ranks, no data-path collective",
-            },
             "configs1_correlation_only": {   # BASELINE.json configs[1]: correlation layer alone, fwd+bwd, 8x256x48x64 fp32
                 "ms_fwd_bwd": round(kernels["corr_fwd"]["ms"] + kernels["corr_bwd"]["ms"], 5),
                 "image_pairs_per_s_per_gpu": round(CORR["B"] / ((kernels["corr_fwd"]["ms"] + kernels["corr_bwd"]["ms"]) * 1e-3), 1),
-            },
-            "roofline": {
-                "kernel": "correlation forward (corr_fwd_f16x2)",
-                "bound": "hbm",
-                "achieved": cf["achieved_GBps"],
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(cf["achieved_GBps"] / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_detail": traffic_detail,
-                "traffic_over_algorithmic": round(traffic / cf["algorithmic_bytes"], 4) if traffic else None,
-                "frac_of_copy_ceiling": round(cf["achieved_GBps"] / copy_gbs, 4),
-                "copy_ceiling_GBps": round(copy_gbs, 1),
-                "copy_ceiling_kernel": copy_kernel,
-                "copy_ceiling_torch_copy_GBps": round(copy_torch, 1),
-                "launch_ms": cf["ms"],
-                "event_pair_floor_ms": round(event_floor_ms, 5),   # the same event pair around a 4-byte fill: rocprofv3's kernel
-                                                                  # durations are shorter than launch_ms by about this much
-                "algorithmic_bytes": cf["algorithmic_bytes"],
             },
             # the same kernel against the matrix-core roof: 3 f16 MFMAs (two-term operand split) per 16x16x32 block product;
             # 480 tasks with neighbour rows inside the image x 8 channel steps x 8 matrix waves x 33 MFMAs x 16384 FLOP
@@ -1065,20 +1081,25 @@ def main():
                         "row-block pair); the kernel is bound by instruction issue and LDS, not by the matrix pipe (DESIGN.md 4.1)"})(
                 480 * 8 * 8 * 33 * 16384),
             "kernels": kernels,
-            "per_rank": per_rank,
-            "rank_balance_fastest_over_slowest": rank_balance,
             "box": {"mfma_probe_TFLOPs": mfma_tflops, "copy_ceiling_GBps": round(copy_gbs, 1), **cold, "xcd_placement": xcd_census,
                     "note": "probes of THIS box: a register-only f16 MFMA stream on every SIMD (first / last five of 40 back-to-back launches; dense "
                             "peak 2500), the streaming copy, and the graded kernel timed alone (operands cache-resident / after a 1 GiB "
                             "fill).  About every second box of the pool runs the whole step 20 % slower (0.23-0.24 vs 0.195-0.205 ms at the "
                             "closing build of round 3, eager and as a hipGraph alike) although all of these probes agree within a few percent across boxes "
                             "(DESIGN.md 5)"},
-        }
-        assert len(per_rank) == world and all(r["finite"] for r in per_rank), per_rank
-        if share:
-            line["dry_run_shared_gpu"] = True
-        if dumped is not None:
-            line["dump_outputs"] = dumped
+        })
+        line["roofline"].update({
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "traffic_detail": traffic_detail,
+            "traffic_over_algorithmic": round(traffic / cf["algorithmic_bytes"], 4) if traffic else None,
+            "frac_of_copy_ceiling": round(cf["achieved_GBps"] / copy_gbs, 4),
+            "copy_ceiling_GBps": round(copy_gbs, 1),
+            "copy_ceiling_kernel": copy_kernel,
+            "copy_ceiling_torch_copy_GBps": round(copy_torch, 1),
+            "event_pair_floor_ms": round(event_floor_ms, 5),   # the same event pair around a 4-byte fill: rocprofv3's kernel
+                                                              # durations are shorter than launch_ms by about this much
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             line["gpu_over_cpu"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
@@ -1088,12 +1109,10 @@ def main():
                 line["gpu_over_cpu_fast"] = round(line["value"] / line["cpu_baseline_fast"]["value"], 1)
             except Exception as exc:
                 line["cpu_baseline_fast"] = {"error": repr(exc)}
-    else:
-        line = None
 
     # The whole FlowNet2C network around the layers (extra key, never `value`).  All ranks take part (gradient all-reduce);
     # a watchdog guarantees the one JSON line even if this pass stalls: it prints the hot-path line and ends the process.
-    if args.model == "on" or (args.model == "auto" and world == 1):
+    if args.full and (args.model == "on" or (args.model == "auto" and world == 1)):
         import threading
 
         def give_up():

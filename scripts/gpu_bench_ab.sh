@@ -16,7 +16,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for n in HEAD ${LIBS:-r2}; do
     L=scripts/ab/libflownet2_hip_$n.so; [ $n = HEAD ] && L=/tmp/head.so
     cp $L flownet2-pytorch_amd/lib/libflownet2_hip.so
-    python bench.py --steps 30 --warmup 5 --no-cpu-baseline --model off > $OUT/bench_$n.json 2>/dev/null; show $OUT/bench_$n.json $n
+    python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --model off > $OUT/bench_$n.json 2>/dev/null; show $OUT/bench_$n.json $n
   done
 done
 cp /tmp/head.so flownet2-pytorch_amd/lib/libflownet2_hip.so

@@ -4,7 +4,7 @@
 # STAGES (any subset, run in this order):
 #   tests     every -m gpu test (TESTS="-k expr" / a path narrows it)          -> <TAG>_gpu_pytest.log
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py (roofline.traffic measured in the run)            -> <TAG>_bench.json
+#   bench     python bench.py --full (roofline.traffic measured in the run)     -> <TAG>_bench.json
 #   prof      rocprofv3 --kernel-trace --stats of the same step                  -> <TAG>_bench_kernel_stats.csv
 #   traffic   fabric traffic of all six kernels (PMC passes of their own)        -> <TAG>_traffic_all.log
 #   sq        SQ counters of the correlation kernels                             -> <TAG>_sq_counters.json
@@ -13,7 +13,7 @@
 #   resample  Resample2d micro + workgroup timeline                              -> <TAG>_resample_*.log
 #   corr      correlation micro (scripts/corr_micro.py)                          -> <TAG>_corr_micro.log
 #   repro     forward reproducibility of harness.FlowNet2 + fused training probe -> <TAG>_forward_reproducibility.log
-#   dry8      `bench.py --gpus 8 --model on` as the shared-GPU dry run           -> <TAG>_bench_gpus8_dry_run.json
+#   dry8      `bench.py --gpus 8 --full --model on` as the shared-GPU dry run    -> <TAG>_bench_gpus8_dry_run.json
 #   extra     whatever EXTRA="cmd" says (one-off experiments)                    -> <TAG>_extra.log
 # Everything lands in gpurun_out/ (scratch); what is judged is copied into profiles/ by hand.
 set -u
@@ -26,7 +26,7 @@ for st in $STAGES; do
   case $st in
     tests)   timeout ${TEST_TIMEOUT:-2400} python -m pytest tests -m gpu -q -rxs $TESTS 2>&1 | tail -${TEST_TAIL:-25} > $OUT/${TAG}_gpu_pytest.log; tail -${TEST_TAIL:-25} $OUT/${TAG}_gpu_pytest.log ;;
     smoke)   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $OUT/${TAG}_gpu_pytest.log ;;
-    bench)   timeout 900 python bench.py ${BENCH_ARGS:-} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit $?"; tail -c 1500 $OUT/${TAG}_bench.json | head -c 1500; echo ;;
+    bench)   timeout 900 python bench.py --full ${BENCH_ARGS:-} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit $?"; tail -c 1500 $OUT/${TAG}_bench.json | head -c 1500; echo ;;
     prof)    ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/${TAG}_prof -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --model off --pmc off > $R/$OUT/${TAG}_prof.log 2>&1 )
              f=$(find $OUT/${TAG}_prof -name "*kernel_stats*.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/${TAG}_bench_kernel_stats.csv && head -12 "$f" | cut -c1-160 ;;
     traffic) bash scripts/gpu_traffic_all.sh > $OUT/${TAG}_traffic_all.log 2>&1; tail -8 $OUT/${TAG}_traffic_all.log | cut -c1-220 ;;
@@ -38,7 +38,7 @@ for st in $STAGES; do
     corr)    timeout 300 python scripts/corr_micro.py ${CORR_ARGS:---algos 4 --iters 30 --bwd 4} 2>/dev/null | grep -v "^{" > $OUT/${TAG}_corr_micro.log; cut -c1-260 $OUT/${TAG}_corr_micro.log | tail -12 ;;
     repro)   timeout 600 python scripts/forward_reproducibility_probe.py > $OUT/${TAG}_forward_reproducibility.log 2>&1; tail -20 $OUT/${TAG}_forward_reproducibility.log | cut -c1-250
              timeout 300 python scripts/fused_training_probe.py >> $OUT/${TAG}_forward_reproducibility.log 2>&1; tail -4 $OUT/${TAG}_forward_reproducibility.log | cut -c1-250 ;;
-    dry8)    FN2_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline --model on --model-steps 3 --model-warmup 1 --model-timeout 1200 > $OUT/${TAG}_bench_gpus8_dry_run.json 2> $OUT/${TAG}_dry8.err; echo "dry8 exit $?"; tail -c 1200 $OUT/${TAG}_bench_gpus8_dry_run.json; tail -3 $OUT/${TAG}_dry8.err ;;
+    dry8)    FN2_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus 8 --steps 5 --warmup 2 --full --no-cpu-baseline --model on --model-steps 3 --model-warmup 1 --model-timeout 1200 > $OUT/${TAG}_bench_gpus8_dry_run.json 2> $OUT/${TAG}_dry8.err; echo "dry8 exit $?"; tail -c 1200 $OUT/${TAG}_bench_gpus8_dry_run.json; tail -3 $OUT/${TAG}_dry8.err ;;
     extra)   bash -c "${EXTRA:-true}" > $OUT/${TAG}_extra.log 2>&1; tail -${EXTRA_TAIL:-30} $OUT/${TAG}_extra.log | cut -c1-260 ;;
     *)       echo "unknown stage $st" ;;
   esac

@@ -71,8 +71,8 @@ def test_bench_gpus_2_model_on():
     share = torch.cuda.device_count() < 2
     if share:
         env["FN2_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--model", "on", "--model-steps", "2", "--model-warmup", "1", "--model-timeout", "900"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--model", "on", "--model-steps", "2", "--model-warmup", "1", "--model-timeout", "900"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -117,7 +117,7 @@ def test_bench_gpus_8_line_explains_itself():
     n = bench.MAX_SHARED_RANKS if share else 8
     if share:
         env["FN2_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--model", "off"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
