@@ -145,16 +145,19 @@ __device__ __forceinline__ unsigned pk_f16(float a, float b)   // v_cvt_pk_f16_f
 }
 
 // One output element as a plain fp32 fma chain over the channels (any finite input): used for outputs whose matrix-core
-// result is non-finite, i.e. an operand did not fit an f16 (or really is inf/nan).
+// result is non-finite, i.e. an operand did not fit an f16 (or really is inf/nan).  An in2 pixel outside the image is an
+// absent term, as in the general kernel: the output is 0 whatever in1 holds.  (Multiplying in1 by a zero there would make an
+// inf / nan of in1 a NaN output in the tasks whose B rows lie partly outside the image, and a 0 where the kernel never forms
+// the block -- B column blocks beyond the image, zero-only tasks.)
 __device__ __forceinline__ float exact_corr(const Args &p, int n, int y, int x, int tj, int ti)
 {
     const long HW = (long)p.H * p.W;
     const int y2 = y + 2 * (tj - DR), x2 = x + 2 * (ti - DR);
+    if (y2 < 0 || y2 >= p.H || x2 < 0 || x2 >= p.W) return 0.0f;
     const float *a = p.in1 + (long)n * p.C * HW + (long)y * p.W + x;
-    const bool inside = y2 >= 0 && y2 < p.H && x2 >= 0 && x2 < p.W;
-    const float *b = p.in2 + (long)n * p.C * HW + (inside ? (long)y2 * p.W + x2 : 0);
+    const float *b = p.in2 + (long)n * p.C * HW + (long)y2 * p.W + x2;
     float s = 0.0f;
-    for (int c = 0; c < p.C; ++c) s = fmaf(a[c * HW], inside ? b[c * HW] : 0.0f, s);
+    for (int c = 0; c < p.C; ++c) s = fmaf(a[c * HW], b[c * HW], s);
     return s;
 }
 

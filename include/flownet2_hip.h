@@ -90,13 +90,15 @@ enum {
                                 v_mfma_f32_16x16x32_f16, fp32 accumulation; the power-of-two scale 2^k -- one per operand and
                                 task, from the mean binary exponent of a 128..256-element sample of the operand -- is exact and
                                 is removed exactly together with the 1/C.
-                                Error bound per operand, relative to the operand's typical (geometric-mean) magnitude m:
-                                max(2^-22 |x| / m, 2^-27), at ANY input magnitude (checked from 2^-27 to 2^13 and on a real
+                                Error bound per operand, relative to the operand's typical magnitude m:
+                                max(2^-22 |x| / m, 2^-24), at ANY input magnitude (checked from 2^-27 to 2^13 and on a real
                                 training gradient, tests/test_gpu_parity.py magnitude sweeps): fp32-class sums, measured
                                 0.65x the fp32 MFMA kernel's error against fp64.  m is what the scale places at 2^-1: the
                                 geometric mean of the sample's non-zero values (mean binary exponent).  Operands above
                                 2^17 m (131072 m: the f16 maximum, 2^16, over 2^-1) do not fit the scaled f16; the outputs
-                                they touch are recomputed by a plain fp32 fma chain (slow, exact semantics incl. inf / nan).  Operands far BELOW m (< 2^-27 m) lose relative accuracy:
+                                they touch are recomputed by a plain fp32 fma chain (slow, exact semantics incl. inf / nan).  Operands BELOW m / 4 lose relative accuracy
+                                (absolute floor 2^-24 m: half the smallest f16 subnormal step, 2^-25, in scaled units where m
+                                sits at 2^-1, f16x2_split.h):
                                 block scaling is not scale-invariant within a task, unlike the reference's fp32 products.
                                 BACKWARD (since round 4): the in1 / in2 operand carries one scale PER CHANNEL (rows of the
                                 A matrix: removed exactly per gradient channel), so "m" above is the channel's own typical
@@ -113,7 +115,29 @@ enum {
                                 half): forward C % 128 == 0, any width (csrc/correlation_f16_fwd.hip); backward C % 64 == 0,
                                 W <= 64 (csrc/correlation_f16_bwd.hip; wider maps: the general kernel).
                                 What FN2_CORR_AUTO picks, forward and backward, for FlowNetC's cost volume; shapes the
-                                launcher declines go on to FN2_CORR_MFMA_F32 / FN2_CORR_DIRECT under AUTO. */
+                                launcher declines go on to FN2_CORR_MFMA_BF16X3 (W <= 64) / FN2_CORR_MFMA_F32 / FN2_CORR_DIRECT
+                                under AUTO.
+                                Per output element (fp32): with S = the element's sum of |products| / nelems and m_a, m_b
+                                bounds of the two operands' typical magnitudes, |out - exact| <= (2^-21 + 2^-22) S
+                                + 2^-24 (m_a sum|b| + m_b sum|a|) / nelems + 3 n 2^-23 S (fp32 sums of 3 n partial
+                                products, n = C forward, 441 backward) + 2^-23 |exact| (the division by a C that is no power
+                                of two) + 2 x 2^-149 (fp32 subnormal results are kept, not flushed).  Outputs an operand above
+                                2^17 m touches meet the fp32 chain's bound (FN2_CORR_MFMA_F32 below).  inf / nan operands: a
+                                read outside the image is an absent term, as in FN2_CORR_DIRECT, not a zero factor; an inf or
+                                nan makes non-finite exactly the outputs (gradients) that pair it with an in-image operand --
+                                those next to the padding stay finite, where the reference's zero-padded buffer gives
+                                0 * inf = nan.  Checked element by element in tests/test_gpu_f32_contract.py.
+   Per-element bounds of the other fp32 / fp64 kernels (tests/corr_contract_ref.py; S as above, n terms per output):
+     FN2_CORR_MFMA_F32      fmaf chain: n 2^-23 S + 2^-23 |exact| (the / C) + subnormal steps; subnormal products
+                            are kept by v_mfma_f32_16x16x4_f32 (measured on an MI355X: operands near 2^-66);
+     FN2_CORR_MFMA_BF16X3   exact 3-term split, 6 of 9 products (the dropped ones < 2^-23 |a b|): 2^-23 S + 6 n 2^-23 S
+                            + 2^-23 |exact|, for operands in fp32's normal range above 2^-110;
+     FN2_CORR_DIRECT fp32   forward: every product rounded, four partial sums (the C % 4 leftover channels in the first):
+                            (floor(C/4) + C % 4 + 3 + k^2) 2^-23 S + 2^-23 |exact|; backward: a sequential sum,
+                            (n + 1) 2^-23 S + 2^-23 |exact|.  Double tensors: the forward the same (products rounded to
+                            float, float accumulator, as the reference), the backward accumulates in double,
+                            (n + 1) 2^-52 S + 2^-52 |exact|;
+     fp64 MFMA (double, AUTO at FlowNetC's configuration): (n + 1) 2^-52 S + 2^-52 |exact|. */
 };
 /* any other algo value: FN2_EINVAL */
 

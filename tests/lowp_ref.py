@@ -129,9 +129,9 @@ def _f16x2_magnitudes(x, block=8):
 
 def delta_bwd_widened(a, b, go, r1, r2, ab1, ab2, md=20, s2=2):
     """Wide (W > 64) half / bf16 backward: the binding widens to fp32, runs the fp32 f16x2 kernel and rounds once.  The header's
-    per-operand bound of that kernel is max(2^-22 |x| / m, 2^-27) relative to m, m the operand's typical magnitude (per channel
+    per-operand bound of that kernel is max(2^-22 |x| / m, 2^-24) relative to m, m the operand's typical magnitude (per channel
     for in1 / in2, per task for gradOutput).  Per gradient element that is a relative term 2^-21 abs_ref (two operands) plus the
-    floor 2^-27 m times the sum of the other operand's magnitudes over the element's terms; the fp32 sums add 3n terms (three
+    floor 2^-24 m times the sum of the other operand's magnitudes over the element's terms; the fp32 sums add 3n terms (three
     partial products each)."""
     pad, k, s1 = md, 1, 1
     ga = go.double().abs()
@@ -143,8 +143,8 @@ def delta_bwd_widened(a, b, go, r1, r2, ab1, ab2, md=20, s2=2):
     sb1, _ = corr_bwd64(ones_x, b.double().abs(), ones_g, pad, k, md, s1, s2)  # sum |in2| over the terms of g1
     _, sa2 = corr_bwd64(a.double().abs(), ones_x, ones_g, pad, k, md, s1, s2)  # sum |in1| over the terms of g2
     n3 = 3 * n_bwd(md, s2, k)
-    d1 = 2.0 ** -21 * ab1 + 2.0 ** -27 * (_f16x2_magnitudes(b) * sg1 + mg * sb1) + n3 * U23 * ab1 + U23 * r1.abs()
-    d2 = 2.0 ** -21 * ab2 + 2.0 ** -27 * (_f16x2_magnitudes(a) * sg2 + mg * sa2) + n3 * U23 * ab2 + U23 * r2.abs()
+    d1 = 2.0 ** -21 * ab1 + 2.0 ** -24 * (_f16x2_magnitudes(b) * sg1 + mg * sb1) + n3 * U23 * ab1 + U23 * r1.abs()
+    d2 = 2.0 ** -21 * ab2 + 2.0 ** -24 * (_f16x2_magnitudes(a) * sg2 + mg * sa2) + n3 * U23 * ab2 + U23 * r2.abs()
     return d1, d2
 
 
