@@ -1,6 +1,8 @@
 // resample2d_cuda.cpp -- pybind module `resample2d_cuda` (drop-in for the reference's module,
 // resample2d_cuda.cc:6-31).  float32, as in the reference (resample2d_kernel.cu:221-230); forward / backward also take bfloat16
-// tensors (mixed-precision training) by widening them to float32 around the float32 kernels -- see widen_bf16 below.
+// tensors (mixed-precision training) by widening them to float32 around the float32 kernels -- see widen_bf16 below.  The fused warp
+// rows (warp_diff_norm_cat, warp_diff_norm and their autograd nodes) take half and bfloat16 tensors natively (fn2_warp_diff_norm*_16:
+// the float32 arithmetic, every result rounded once); only a pair that itself needs a gradient is widened around the float32 node.
 #include "binding_common.h"
 
 using namespace fn2b;
@@ -21,6 +23,13 @@ static bool deterministic() { return at::globalContext().deterministicAlgorithms
 // straight from the caching allocator of the current device (at::empty would fill it under the deterministic flag; the entry point clears
 // it on the stream itself); released to the allocator when the DataPtr goes, as a temporary tensor is
 static c10::DataPtr det_workspace(size_t bytes) { return c10::GetAllocator(c10::DeviceType::CUDA)->allocate(bytes); }
+
+// half / bfloat16: the element types the 16-bit entry points of the fused warp rows take
+static bool is_lowp(const at::Tensor &t) { return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16; }
+static void check_warp_dtype(const at::Tensor &t, const char *op)
+{
+    TORCH_CHECK(t.scalar_type() == at::kFloat || is_lowp(t), op, ": float32, float16 or bfloat16 tensors expected, got ", t.scalar_type());
+}
 
 static void strides4(const at::Tensor &t, int64_t s[4])
 {
@@ -116,7 +125,7 @@ int warp_diff_norm_cat_hip(at::Tensor &pair, at::Tensor &flow, at::Tensor &outpu
     check_gpu(pair, op, "pair");
     check_same(pair, flow, op, "flow");
     check_same(pair, output, op, "output");
-    TORCH_CHECK(pair.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", pair.scalar_type());
+    check_warp_dtype(pair, op);
     TORCH_CHECK(pair.dim() == 4 && flow.dim() == 4 && output.dim() == 4, op, ": tensors must be 4-D");
     TORCH_CHECK(pair.size(1) % 2 == 0 && pair.size(1) > 0, op, ": pair must hold two images (even channel count), got ",
                 pair.sizes());
@@ -128,6 +137,11 @@ int warp_diff_norm_cat_hip(at::Tensor &pair, at::Tensor &flow, at::Tensor &outpu
                 op, ": output must be contiguous [", B, ", ", 3 * C + 3, ", ", H, ", ", W, "], got ", output.sizes());
     c10::DeviceGuard guard(pair.device());
     at::Tensor p = pair.contiguous(), f = flow.contiguous();
+    if (is_lowp(pair)) {
+        check_rc(fn2_warp_diff_norm_cat_16(p.data_ptr(), f.data_ptr(), output.data_ptr(), dtype_of(pair, op), (float)div_flow, B, C, H, W,
+                                           bilinear ? 1 : 0, current_stream(pair)), op);
+        return 1;
+    }
     check_rc(fn2_warp_diff_norm_cat(p.data_ptr<float>(), f.data_ptr<float>(), output.data_ptr<float>(), (float)div_flow,
                                     B, C, H, W, bilinear ? 1 : 0, current_stream(pair)), op);
     return 1;
@@ -140,18 +154,19 @@ int warp_diff_norm_cat_backward_hip(at::Tensor &pair, at::Tensor &flow, at::Tens
     const char *op = "resample2d_cuda.warp_diff_norm_cat_backward";
     check_gpu(pair, op, "pair");
     check_same(pair, flow, op, "flow");
-    check_same(pair, output, op, "output");
     check_same(pair, gradOutput, op, "gradOutput");
     check_same(pair, gradFlow, op, "gradFlow");
-    TORCH_CHECK(pair.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", pair.scalar_type());
-    TORCH_CHECK(pair.dim() == 4 && flow.dim() == 4 && output.dim() == 4 && gradOutput.dim() == 4, op, ": tensors must be 4-D");
+    check_warp_dtype(pair, op);
+    const bool lowp = is_lowp(pair);   // half / bfloat16: flow gradient only, warp and norm recomputed; `output` is not read
+    if (!lowp) check_same(pair, output, op, "output");
+    TORCH_CHECK(pair.dim() == 4 && flow.dim() == 4 && gradOutput.dim() == 4 && (lowp || output.dim() == 4), op, ": tensors must be 4-D");
     TORCH_CHECK(pair.size(1) % 2 == 0 && pair.size(1) > 0, op, ": pair must hold two images, got ", pair.sizes());
     const int B = pair.size(0), C = pair.size(1) / 2, H = pair.size(2), W = pair.size(3);
     TORCH_CHECK(flow.size(0) == B && flow.size(1) == 2 && flow.size(2) == H && flow.size(3) == W, op, ": flow ", flow.sizes(),
                 " does not match pair ", pair.sizes());
-    TORCH_CHECK(output.sizes() == gradOutput.sizes() && output.size(0) == B && output.size(1) == 3 * C + 3 && output.size(2) == H &&
-                    output.size(3) == W, op, ": output / gradOutput must be [", B, ", ", 3 * C + 3, ", ", H, ", ", W, "]");
-    TORCH_CHECK(pair.is_contiguous() && flow.is_contiguous() && output.is_contiguous(), op, ": pair, flow and output must be contiguous");
+    TORCH_CHECK((lowp || output.sizes() == gradOutput.sizes()) && gradOutput.size(0) == B && gradOutput.size(1) == 3 * C + 3 &&
+                    gradOutput.size(2) == H && gradOutput.size(3) == W, op, ": output / gradOutput must be [", B, ", ", 3 * C + 3, ", ", H, ", ", W, "]");
+    TORCH_CHECK(pair.is_contiguous() && flow.is_contiguous() && (lowp || output.is_contiguous()), op, ": pair, flow and output must be contiguous");
     TORCH_CHECK(gradFlow.sizes() == flow.sizes() && gradFlow.is_contiguous(), op, ": gradFlow must be contiguous and shaped like flow");
     const bool want_pair = gradPair.defined() && gradPair.numel() > 0;
     if (want_pair) {
@@ -160,6 +175,13 @@ int warp_diff_norm_cat_backward_hip(at::Tensor &pair, at::Tensor &flow, at::Tens
     }
     c10::DeviceGuard guard(pair.device());
     at::Tensor go = gradOutput.contiguous();
+    if (lowp) {
+        TORCH_CHECK(!want_pair, op, ": the 16-bit backward gives the flow gradient only (the pair's gradient is a float32 scatter: widen the "
+                                    "tensors, or use warp_diff_norm_cat_apply, which does)");
+        check_rc(fn2_warp_diff_norm_cat_backward_16(pair.data_ptr(), flow.data_ptr(), go.data_ptr(), gradFlow.data_ptr(), dtype_of(pair, op),
+                                                    (float)div_flow, B, C, H, W, bilinear ? 1 : 0, current_stream(pair)), op);
+        return 1;
+    }
     if (want_pair && deterministic()) {   // the second image's gradient is scattered: fixed-point sums under the deterministic flag
         const size_t wsb = fn2_warp_diff_norm_cat_backward_det_workspace_bytes(B, C, H, W);
         c10::DataPtr ws = det_workspace(wsb);
@@ -181,7 +203,7 @@ at::Tensor warp_diff_norm_hip(at::Tensor &pair, at::Tensor &flow, bool bilinear)
     const char *op = "resample2d_cuda.warp_diff_norm";
     check_gpu(pair, op, "pair");
     check_same(pair, flow, op, "flow");
-    TORCH_CHECK(pair.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", pair.scalar_type());
+    check_warp_dtype(pair, op);
     TORCH_CHECK(pair.dim() == 4 && flow.dim() == 4 && pair.size(1) % 2 == 0 && pair.size(1) > 0, op, ": pair must be 4-D with two images");
     const int B = pair.size(0), C = pair.size(1) / 2, H = pair.size(2), W = pair.size(3);
     TORCH_CHECK(flow.size(0) == B && flow.size(1) == 2 && flow.size(2) == H && flow.size(3) == W, op, ": flow ", flow.sizes(),
@@ -189,6 +211,11 @@ at::Tensor warp_diff_norm_hip(at::Tensor &pair, at::Tensor &flow, bool bilinear)
     c10::DeviceGuard guard(pair.device());
     at::Tensor p = pair.contiguous(), f = flow.contiguous();
     at::Tensor out = at::empty({B, 1, H, W}, pair.options());
+    if (is_lowp(pair)) {
+        check_rc(fn2_warp_diff_norm_16(p.data_ptr(), f.data_ptr(), out.data_ptr(), dtype_of(pair, op), B, C, H, W, bilinear ? 1 : 0,
+                                       current_stream(pair)), op);
+        return out;
+    }
     check_rc(fn2_warp_diff_norm(p.data_ptr<float>(), f.data_ptr<float>(), out.data_ptr<float>(), B, C, H, W, bilinear ? 1 : 0,
                                 current_stream(pair)), op);
     return out;
@@ -199,19 +226,26 @@ at::Tensor warp_diff_norm_backward_hip(at::Tensor &pair, at::Tensor &flow, at::T
     const char *op = "resample2d_cuda.warp_diff_norm_backward";
     check_gpu(pair, op, "pair");
     check_same(pair, flow, op, "flow");
-    check_same(pair, norm, op, "norm");
     check_same(pair, gradNorm, op, "gradNorm");
-    TORCH_CHECK(pair.scalar_type() == at::kFloat, op, ": float32 tensors expected, got ", pair.scalar_type());
+    check_warp_dtype(pair, op);
+    const bool lowp = is_lowp(pair);   // half / bfloat16: the norm is recomputed, `norm` is not read (an empty tensor will do)
+    if (!lowp) check_same(pair, norm, op, "norm");
     TORCH_CHECK(pair.dim() == 4 && flow.dim() == 4 && pair.size(1) % 2 == 0 && pair.size(1) > 0, op, ": pair must be 4-D with two images");
     const int B = pair.size(0), C = pair.size(1) / 2, H = pair.size(2), W = pair.size(3);
     TORCH_CHECK(flow.size(0) == B && flow.size(1) == 2 && flow.size(2) == H && flow.size(3) == W, op, ": flow ", flow.sizes(),
                 " does not match pair ", pair.sizes());
-    TORCH_CHECK(norm.sizes() == gradNorm.sizes() && norm.dim() == 4 && norm.size(0) == B && norm.size(1) == 1 && norm.size(2) == H &&
-                    norm.size(3) == W, op, ": norm / gradNorm must be [", B, ", 1, ", H, ", ", W, "]");
-    TORCH_CHECK(pair.is_contiguous() && flow.is_contiguous() && norm.is_contiguous(), op, ": pair, flow and norm must be contiguous");
+    TORCH_CHECK(gradNorm.dim() == 4 && gradNorm.size(0) == B && gradNorm.size(1) == 1 && gradNorm.size(2) == H && gradNorm.size(3) == W, op,
+                ": norm / gradNorm must be [", B, ", 1, ", H, ", ", W, "]");
+    TORCH_CHECK(lowp || norm.sizes() == gradNorm.sizes(), op, ": norm / gradNorm must be [", B, ", 1, ", H, ", ", W, "]");
+    TORCH_CHECK(pair.is_contiguous() && flow.is_contiguous() && (lowp || norm.is_contiguous()), op, ": pair, flow and norm must be contiguous");
     c10::DeviceGuard guard(pair.device());
     at::Tensor gn = gradNorm.contiguous();
     at::Tensor gflow = at::empty(flow.sizes(), flow.options());
+    if (lowp) {
+        check_rc(fn2_warp_diff_norm_backward_16(pair.data_ptr(), flow.data_ptr(), gn.data_ptr(), gflow.data_ptr(), dtype_of(pair, op), B, C, H, W,
+                                                bilinear ? 1 : 0, current_stream(pair)), op);
+        return gflow;
+    }
     check_rc(fn2_warp_diff_norm_backward(pair.data_ptr<float>(), flow.data_ptr<float>(), norm.data_ptr<float>(), gn.data_ptr<float>(),
                                          gflow.data_ptr<float>(), B, C, H, W, bilinear ? 1 : 0, current_stream(pair)), op);
     return gflow;
@@ -280,58 +314,84 @@ at::Tensor resample2d_apply(const at::Tensor &input1, const at::Tensor &input2, 
     return Resample2dOp::apply(input1, input2, kernel_size, bilinear);
 }
 
-// models.py:133-138 as one differentiable op (fn2_warp_diff_norm_cat / fn2_warp_diff_norm_cat_backward)
+// models.py:133-138 as one differentiable op (fn2_warp_diff_norm_cat / fn2_warp_diff_norm_cat_backward).
+// Element types: float32 as ever.  x and flow of the SAME 16-bit type (half, bfloat16) and no gradient wanted for x: the native 16-bit
+// entry points, forward and backward; the backward recomputes the warp and the norm, so the node does not save its output.  A 16-bit x
+// that needs a gradient itself, or mixed types (float32 x with a bfloat16 flow under autocast): widened around the float32 kernels,
+// every result rounded once to its input's type (the output to x's).
 struct WarpDiffNormCatOp : public torch::autograd::Function<WarpDiffNormCatOp> {
-    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &x_, const at::Tensor &flow_, double div_flow, bool bilinear)
+    // x_needs_grad: x.requires_grad() under the caller's grad mode (grad mode is off in here)
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &x_, const at::Tensor &flow_, double div_flow, bool bilinear, bool x_needs_grad)
     {
         const char *op = "WarpDiffNormCat";
         check_gpu(x_, op, "x");
-        check_same(x_, flow_, op, "flow");
+        check_gpu(flow_, op, "flow");
+        TORCH_CHECK(x_.device() == flow_.device(), op, ": flow is on ", flow_.device(), ", expected ", x_.device());
+        check_warp_dtype(x_, op);
+        check_warp_dtype(flow_, op);
         TORCH_CHECK(x_.dim() == 4 && x_.size(1) % 2 == 0 && x_.size(1) > 0, op, ": x must be 4-D with two images, got ", x_.sizes());
         c10::DeviceGuard guard(x_.device());
-        at::Tensor x = x_.contiguous(), flow = flow_.contiguous();
+        const bool same = x_.scalar_type() == flow_.scalar_type();
+        const bool native16 = same && is_lowp(x_) && !x_needs_grad;
+        const bool widen = !native16 && (is_lowp(x_) || !same);
+        at::Tensor x = (widen ? x_.to(at::kFloat) : x_).contiguous(), flow = (widen ? flow_.to(at::kFloat) : flow_).contiguous();
         const int64_t c2 = x.size(1);
         at::Tensor out = at::empty({x.size(0), c2 + c2 / 2 + 3, x.size(2), x.size(3)}, x.options());
         warp_diff_norm_cat_hip(x, flow, out, div_flow, bilinear);
-        ctx->save_for_backward({x, flow, out});
+        if (native16) ctx->save_for_backward({x, flow});
+        else ctx->save_for_backward({x, flow, out});
         ctx->saved_data["d"] = div_flow;
         ctx->saved_data["b"] = bilinear;
-        return out;
+        ctx->saved_data["tx"] = (int64_t)x_.scalar_type();
+        ctx->saved_data["tf"] = (int64_t)flow_.scalar_type();
+        return widen ? out.to(x_.scalar_type()) : out;
     }
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
         check_once_differentiable(grad_outputs, "WarpDiffNormCatFunction.backward");
         const bool need_x = ctx->needs_input_grad(0), need_flow = ctx->needs_input_grad(1);
-        if (!(need_x || need_flow)) return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        if (!(need_x || need_flow)) return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
         auto saved = ctx->get_saved_variables();
-        at::Tensor x = saved[0], flow = saved[1], out = saved[2];
+        at::Tensor x = saved[0], flow = saved[1], out = saved.size() > 2 ? saved[2] : at::Tensor();
         c10::DeviceGuard guard(x.device());
-        at::Tensor go = grad_outputs[0].contiguous();
+        at::Tensor go = grad_outputs[0].to(x.scalar_type()).contiguous();   // (widened path: the 16-bit gradient widened, exact)
         at::Tensor gx = need_x ? at::empty_like(x) : at::empty({0}, x.options());
         at::Tensor gflow = at::empty_like(flow);
+        if (!out.defined()) out = at::empty({0}, x.options());
         warp_diff_norm_cat_backward_hip(x, flow, out, go, gx, gflow, ctx->saved_data["d"].toDouble(), ctx->saved_data["b"].toBool());
-        return {need_x ? gx : at::Tensor(), need_flow ? gflow : at::Tensor(), at::Tensor(), at::Tensor()};
+        const auto tx = (at::ScalarType)ctx->saved_data["tx"].toInt(), tf = (at::ScalarType)ctx->saved_data["tf"].toInt();
+        return {need_x ? gx.to(tx) : at::Tensor(), need_flow ? gflow.to(tf) : at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
 at::Tensor warp_diff_norm_cat_apply(const at::Tensor &x, const at::Tensor &flow, double div_flow, bool bilinear)
 {
-    return WarpDiffNormCatOp::apply(x, flow, div_flow, bilinear);
+    return WarpDiffNormCatOp::apply(x, flow, div_flow, bilinear, x.requires_grad() && at::GradMode::is_enabled());
 }
 
 // models.py:157-161 / :170-174 as one differentiable op (flow gradient only; the caller composes the unfused layers when the pair
-// itself needs a gradient)
+// itself needs a gradient).  Element types as WarpDiffNormCatOp: same-type half / bfloat16 native (nothing but x and flow saved),
+// mixed types widened.
 struct WarpDiffNormOp : public torch::autograd::Function<WarpDiffNormOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &x_, const at::Tensor &flow_, bool bilinear)
     {
-        check_gpu(x_, "WarpDiffNorm", "x");
+        const char *op = "WarpDiffNorm";
+        check_gpu(x_, op, "x");
+        check_gpu(flow_, op, "flow");
+        check_warp_dtype(x_, op);
+        check_warp_dtype(flow_, op);
         c10::DeviceGuard guard(x_.device());
-        at::Tensor x = x_.contiguous(), flow = flow_.contiguous();
+        const bool same = x_.scalar_type() == flow_.scalar_type();
+        const bool native16 = same && is_lowp(x_);
+        const bool widen = !same;
+        at::Tensor x = (widen ? x_.to(at::kFloat) : x_).contiguous(), flow = (widen ? flow_.to(at::kFloat) : flow_).contiguous();
         at::Tensor norm = warp_diff_norm_hip(x, flow, bilinear);
-        ctx->save_for_backward({x, flow, norm});
+        if (native16) ctx->save_for_backward({x, flow});
+        else ctx->save_for_backward({x, flow, norm});
         ctx->saved_data["b"] = bilinear;
-        return norm;
+        ctx->saved_data["tf"] = (int64_t)flow_.scalar_type();
+        return widen ? norm.to(x_.scalar_type()) : norm;
     }
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
@@ -339,9 +399,10 @@ struct WarpDiffNormOp : public torch::autograd::Function<WarpDiffNormOp> {
         check_once_differentiable(grad_outputs, "WarpDiffNormFunction.backward");
         if (!ctx->needs_input_grad(1)) return {at::Tensor(), at::Tensor(), at::Tensor()};
         auto saved = ctx->get_saved_variables();
-        at::Tensor x = saved[0], flow = saved[1], norm = saved[2];
-        at::Tensor gn = grad_outputs[0];
-        return {at::Tensor(), warp_diff_norm_backward_hip(x, flow, norm, gn, ctx->saved_data["b"].toBool()), at::Tensor()};
+        at::Tensor x = saved[0], flow = saved[1], norm = saved.size() > 2 ? saved[2] : at::empty({0}, saved[0].options());
+        at::Tensor gn = grad_outputs[0].to(x.scalar_type());
+        at::Tensor gflow = warp_diff_norm_backward_hip(x, flow, norm, gn, ctx->saved_data["b"].toBool());
+        return {at::Tensor(), gflow.to((at::ScalarType)ctx->saved_data["tf"].toInt()), at::Tensor()};
     }
 };
 

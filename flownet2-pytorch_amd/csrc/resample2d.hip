@@ -17,32 +17,11 @@
 #include <type_traits>
 
 #include "fn2_common.h"
+#include "resample2d_common.h"
 #include "fn2_debug.h"
 #include "corr_params.h"
 
 namespace fn2 {
-
-typedef float __attribute__((ext_vector_type(4))) f4;
-
-struct ImgStrides { long b, c, h, w; };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// int(floor(xf)) with CUDA's saturating float->int conversion (cvt.rzi.s32.f32; NaN -> 0).
-__device__ __forceinline__ int f2i_sat(float v)
-{
-    if (!(v == v)) return 0;
-    if (v >= 2147483520.0f) return 2147483647;
-    if (v <= -2147483648.0f) return (-2147483647 - 1);
-    return (int)v;
-}
-__device__ __forceinline__ int d2i_sat(double v)
-{
-    if (!(v == v)) return 0;
-    if (v >= 2147483647.0) return 2147483647;
-    if (v <= -2147483648.0) return (-2147483647 - 1);
-    return (int)v;
-}
 
 // ---------------------------------------------------------------- deterministic grad_input1: fixed-point accumulation
 // The contract (include/flownet2_hip.h, fn2_resample2d_backward_det): per plane (b, c) of the scattered gradient, M = max |g|,

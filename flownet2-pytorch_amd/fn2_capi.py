@@ -25,6 +25,7 @@ EXPORTS = [
     "fn2_multiscale_loss_fused", "fn2_multiscale_scale_grads",
     "fn2_resample2d_backward_det_workspace_bytes", "fn2_resample2d_backward_det",
     "fn2_warp_diff_norm_cat_backward_det_workspace_bytes", "fn2_warp_diff_norm_cat_backward_det",
+    "fn2_warp_diff_norm_cat_16", "fn2_warp_diff_norm_cat_backward_16", "fn2_warp_diff_norm_16", "fn2_warp_diff_norm_backward_16",
 ]
 
 # profiling / ablation entry points (csrc/fn2_debug.h): not in include/flownet2_hip.h, results wrong by design; exported by
@@ -209,6 +210,61 @@ def warp_diff_norm_backward(pair, flow, norm, grad_norm, bilinear=True):
     with torch.cuda.device_of(pair):
         check(lib().fn2_warp_diff_norm_backward(_p(pair), _p(flow), _p(norm), _p(grad_norm), _p(gflow), B, C2 // 2, H, W,
                                                 1 if bilinear else 0, _stream(pair)), "fn2_warp_diff_norm_backward")
+    return gflow
+
+
+def _check16(pair, *others):
+    import torch
+    assert pair.dtype in (torch.float16, torch.bfloat16) and pair.shape[1] % 2 == 0
+    for t in (pair,) + others:
+        assert t.is_contiguous() and t.dtype == pair.dtype
+
+
+def warp_diff_norm_cat_16(pair, flow, div_flow=20.0, bilinear=True, out=None):
+    """fn2_warp_diff_norm_cat_16: the concat row on half / bfloat16 tensors as they are (``out``: a preallocated result)."""
+    import torch
+    B, C2, H, W = pair.shape
+    _check16(pair, flow)
+    if out is None:
+        out = torch.full((B, 3 * (C2 // 2) + 3, H, W), float("nan"), dtype=pair.dtype, device=pair.device)
+    with torch.cuda.device_of(pair):
+        check(lib().fn2_warp_diff_norm_cat_16(_p(pair), _p(flow), _p(out), _dtype_code(pair), ctypes.c_float(div_flow), B, C2 // 2, H, W,
+                                              1 if bilinear else 0, _stream(pair)), "fn2_warp_diff_norm_cat_16")
+    return out
+
+
+def warp_diff_norm_cat_backward_16(pair, flow, grad_cat, div_flow=20.0, bilinear=True):
+    """fn2_warp_diff_norm_cat_backward_16: the flow gradient of the concat row, the warp and the norm recomputed."""
+    import torch
+    B, C2, H, W = pair.shape
+    _check16(pair, flow, grad_cat)
+    gflow = torch.full_like(flow, float("nan"))
+    with torch.cuda.device_of(pair):
+        check(lib().fn2_warp_diff_norm_cat_backward_16(_p(pair), _p(flow), _p(grad_cat), _p(gflow), _dtype_code(pair),
+                                                       ctypes.c_float(div_flow), B, C2 // 2, H, W, 1 if bilinear else 0, _stream(pair)),
+              "fn2_warp_diff_norm_cat_backward_16")
+    return gflow
+
+
+def warp_diff_norm_16(pair, flow, bilinear=True):
+    import torch
+    B, C2, H, W = pair.shape
+    _check16(pair, flow)
+    out = torch.full((B, 1, H, W), float("nan"), dtype=pair.dtype, device=pair.device)
+    with torch.cuda.device_of(pair):
+        check(lib().fn2_warp_diff_norm_16(_p(pair), _p(flow), _p(out), _dtype_code(pair), B, C2 // 2, H, W, 1 if bilinear else 0,
+                                          _stream(pair)), "fn2_warp_diff_norm_16")
+    return out
+
+
+def warp_diff_norm_backward_16(pair, flow, grad_norm, bilinear=True):
+    import torch
+    B, C2, H, W = pair.shape
+    _check16(pair, flow, grad_norm)
+    gflow = torch.full_like(flow, float("nan"))
+    with torch.cuda.device_of(pair):
+        check(lib().fn2_warp_diff_norm_backward_16(_p(pair), _p(flow), _p(grad_norm), _p(gflow), _dtype_code(pair), B, C2 // 2, H, W,
+                                                   1 if bilinear else 0, _stream(pair)), "fn2_warp_diff_norm_backward_16")
     return gflow
 
 

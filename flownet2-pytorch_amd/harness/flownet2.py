@@ -204,6 +204,8 @@ class FlowNet2(nn.Module):
         layers under autograd as rounds 1-4 did."""
         dt = x.dtype
         if not torch.is_grad_enabled() or self.fused_training:
+            if dt in (torch.float16, torch.bfloat16) and flow.dtype == dt:   # the native 16-bit row: same bits, no fp32 round trip
+                return self.warp_cat(x, flow)
             return self.warp_cat(x.float(), flow.float()).to(dt)
         warped = resample(x[:, 3:].float(), flow.float())
         norm = self.channelnorm(x[:, :3].float() - warped)
@@ -214,6 +216,8 @@ class FlowNet2(nn.Module):
         (WarpDiffNorm, differentiable w.r.t. the flow); `fused_training = False` composes the separate layers."""
         f = flow.float()
         if not torch.is_grad_enabled() or self.fused_training:
+            if x.dtype in (torch.float16, torch.bfloat16) and flow.dtype == x.dtype:   # the native 16-bit row, as in _warp_concat
+                return self.channelnorm(f).to(x.dtype), self.warp_err(x, flow)
             return self.channelnorm(f).to(x.dtype), self.warp_err(x.float(), f).to(x.dtype)
         warped = resample(x[:, 3:].float(), f)
         return self.channelnorm(f).to(x.dtype), self.channelnorm(x[:, :3].float() - warped).to(x.dtype)

@@ -5,7 +5,9 @@ Same public names and signatures as the reference wrapper
 kernel_size, bilinear)`` and ``Resample2d(kernel_size=1, bilinear=True)``; output shape is
 (B, C_img, H, W) with B, H, W taken from the flow (reference :16-18).  float32, as in the
 reference; bfloat16 tensors (autocast) are widened to float32 around the float32 kernels and each
-result is rounded to bfloat16 once.  Unlike the reference Module (:48) the image is NOT made contiguous first: the HIP
+result is rounded to bfloat16 once (Resample2d refuses half, as the reference does).  The fused rows
+WarpDiffNormCat / WarpDiffNorm take half and bfloat16 tensors natively: 16-bit kernels with the float32
+arithmetic inside, bit-identical to the widened float32 call rounded once.  Unlike the reference Module (:48) the image is NOT made contiguous first: the HIP
 kernel honours input1's strides, which saves a full copy of the channel slice models.py:133
 passes in.
 """
@@ -15,6 +17,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import resample2d_cuda  # built by flownet2-pytorch_amd/build.py; no fallback on purpose
+
+_LOWP = (torch.float16, torch.bfloat16)   # the fused rows' native 16-bit element types
 
 
 class Resample2dFunction(Function):
@@ -73,27 +77,35 @@ class WarpDiffNormCatFunction(Function):
     def apply(cls, x, flow, div_flow, bilinear):
         return resample2d_cuda.warp_diff_norm_cat_apply(x, flow, float(div_flow), bool(bilinear))
 
+    # Element types, as the C++ node: x and flow of the same 16-bit type and no gradient for x -> the native 16-bit kernels (the backward
+    # recomputes warp and norm: the output is not saved); a 16-bit x that needs a gradient, or mixed types -> widened around the
+    # float32 kernels, each result rounded once
     @staticmethod
     def forward(ctx, x, flow, div_flow, bilinear):
+        ctx.types = (x.dtype, flow.dtype)
+        native16 = x.dtype == flow.dtype and x.dtype in _LOWP and not ctx.needs_input_grad[0]
+        if not native16 and (x.dtype in _LOWP or x.dtype != flow.dtype):
+            x, flow = x.float(), flow.float()
         x, flow = x.contiguous(), flow.contiguous()
         b, c2, h, w = x.shape
         out = x.new_empty((b, c2 + c2 // 2 + 3, h, w))
         resample2d_cuda.warp_diff_norm_cat(x, flow, out, float(div_flow), bool(bilinear))
-        ctx.save_for_backward(x, flow, out)
+        ctx.save_for_backward(*((x, flow) if native16 else (x, flow, out)))
         ctx.div_flow, ctx.bilinear = float(div_flow), bool(bilinear)
-        return out
+        return out.to(ctx.types[0])
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        x, flow, out = ctx.saved_tensors
+        x, flow = ctx.saved_tensors[:2]
+        out = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else x.new_empty(0)
         need_x, need_flow = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_x or need_flow):
             return None, None, None, None
         grad_x = torch.empty_like(x) if need_x else x.new_empty(0)
         grad_flow = torch.empty_like(flow)
-        resample2d_cuda.warp_diff_norm_cat_backward(x, flow, out, grad_out.contiguous(), grad_x, grad_flow, ctx.div_flow, ctx.bilinear)
-        return (grad_x if need_x else None), (grad_flow if need_flow else None), None, None
+        resample2d_cuda.warp_diff_norm_cat_backward(x, flow, out, grad_out.to(x.dtype).contiguous(), grad_x, grad_flow, ctx.div_flow, ctx.bilinear)
+        return (grad_x.to(ctx.types[0]) if need_x else None), (grad_flow.to(ctx.types[1]) if need_flow else None), None, None
 
 
 class WarpDiffNormCat(nn.Module):
@@ -112,8 +124,6 @@ class WarpDiffNormCat(nn.Module):
         self.bilinear = bilinear
 
     def forward(self, x, flow):
-        if x.dtype == torch.bfloat16:   # bf16 (autocast): widened around the fp32 kernels, the result rounded to bf16 once
-            return WarpDiffNormCatFunction.apply(x.float(), flow.float(), float(self.div_flow), self.bilinear).to(torch.bfloat16)
         return WarpDiffNormCatFunction.apply(x, flow, float(self.div_flow), self.bilinear)
 
 
@@ -129,18 +139,25 @@ class WarpDiffNormFunction(Function):
 
     @staticmethod
     def forward(ctx, x, flow, bilinear):
+        ctx.types = (x.dtype, flow.dtype)
+        native16 = x.dtype == flow.dtype and x.dtype in _LOWP
+        if x.dtype != flow.dtype:   # mixed types: widened around the float32 kernels
+            x, flow = x.float(), flow.float()
         x, flow = x.contiguous(), flow.contiguous()
         norm = resample2d_cuda.warp_diff_norm(x, flow, bool(bilinear))
-        ctx.save_for_backward(x, flow, norm)
+        ctx.save_for_backward(*((x, flow) if native16 else (x, flow, norm)))   # the 16-bit backward recomputes the norm
         ctx.bilinear = bool(bilinear)
-        return norm
+        return norm.to(ctx.types[0])
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_norm):
-        x, flow, norm = ctx.saved_tensors
-        grad_flow = resample2d_cuda.warp_diff_norm_backward(x, flow, norm, grad_norm.contiguous(), ctx.bilinear) if ctx.needs_input_grad[1] else None
-        return None, grad_flow, None
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        x, flow = ctx.saved_tensors[:2]
+        norm = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else x.new_empty(0)
+        grad_flow = resample2d_cuda.warp_diff_norm_backward(x, flow, norm, grad_norm.to(x.dtype).contiguous(), ctx.bilinear)
+        return None, grad_flow.to(ctx.types[1]), None
 
 
 class WarpDiffNorm(nn.Module):
@@ -152,11 +169,11 @@ class WarpDiffNorm(nn.Module):
         self.bilinear = bilinear
 
     def forward(self, x, flow):
-        if x.dtype == torch.bfloat16:   # bf16 (autocast): widened around the fp32 kernels, the result rounded to bf16 once
-            return self.forward(x.float(), flow.float()).to(torch.bfloat16)
         if x.requires_grad and torch.is_grad_enabled():
             # the pair itself wants a gradient (not the case in FlowNet2, where it is the input): the unfused layers under autograd
             from networks.channelnorm_package.channelnorm import ChannelNormFunction
+            if x.dtype in _LOWP:   # Resample2d is float32 (and refuses half): widened first, the result rounded once
+                return self.forward(x.float(), flow.float()).to(x.dtype)
             c = x.shape[1] // 2
             # (flow made contiguous like the fused path does: the same module must not accept a strided flow or raise depending on
             # whether the pair wants a gradient -- ADVICE r5)

@@ -53,8 +53,9 @@ extern "C" {
  * for resample2d -- resample2d_kernel.cu:221,269,298) */
 enum { FN2_F32 = 0, FN2_F16 = 1, FN2_F64 = 2, FN2_BF16 = 3 };
 /* FN2_BF16 (bfloat16: fp32's exponent range, 8 significant bits) is accepted by the correlation and ChannelNorm entry points
- * (forward, _ex, _fused, backward, _ex, _fused, _fused_workspace_bytes; fn2_channelnorm_forward / _backward).  The Resample2d,
- * warp-diff-norm and multiscale entry points stay float32.  Correlation selectors for bf16 tensors are those of half:
+ * (forward, _ex, _fused, backward, _ex, _fused, _fused_workspace_bytes; fn2_channelnorm_forward / _backward) and, like
+ * FN2_F16, by the fused warp rows' 16-bit entry points (fn2_warp_diff_norm*_16 below).  The Resample2d, float32 warp-diff-norm
+ * and multiscale entry points stay float32.  Correlation selectors for bf16 tensors are those of half:
  * FN2_CORR_AUTO and FN2_CORR_MFMA_F16X2 take the bf16 matrix kernels (v_mfma_f32_16x16x32_bf16, the half kernels' tilings) where
  * half's preconditions hold, FN2_CORR_DIRECT the general kernel; FN2_CORR_MFMA_F32 / _BF16X3 return what they return for half
  * (FN2_EUNSUPPORTED).  Products of two bf16 values are exact in fp32, sums are fp32, every result is rounded to bf16 once (round
@@ -322,6 +323,44 @@ int fn2_warp_diff_norm_cat_backward_det(const float *pair, const float *flow, co
 int fn2_warp_diff_norm(const float *pair, const float *flow, float *out_norm, int B, int C, int H, int W, int bilinear, void *stream);
 int fn2_warp_diff_norm_backward(const float *pair, const float *flow, const float *norm, const float *grad_norm, float *grad_flow,
                                 int B, int C, int H, int W, int bilinear, void *stream);
+
+/* The fused warp rows on 16-bit tensors: fn2_warp_diff_norm_cat, fn2_warp_diff_norm and their flow-gradient backward passes taking half
+ * (FN2_F16) or bfloat16 (FN2_BF16) tensors as they are -- 16 bits in memory, the float32 kernels' arithmetic inside, one launch and no
+ * float32 temporaries.  Added without an ABI version change (FN2_ABI_VERSION stays 3): a caller detects these entry points by looking
+ * up their symbols, as the _det entry points are detected.
+ *
+ * Contract: every element a 16-bit entry point writes has exactly the bits of the float32 entry point run on the exactly widened
+ * inputs, its float32 result rounded to the 16-bit type ONCE, round to nearest even (overflow -> +-inf, subnormal results kept, NaN
+ * stays NaN).  Hence
+ *  - forward: the norm plane is the square root of the float32 sum of squares of first image - warped with the warped values
+ *    UNROUNDED, not of the stored 16-bit ones; the copied planes (the pair) are exact; flow / div_flow is
+ *    (float)flow * (1.0f / div_flow), rounded once;
+ *  - backward: the float32 entry points read the warped image and the norm back from the forward's float32 output; a 16-bit output
+ *    holds them rounded, so the 16-bit backward passes take NO forward output: they recompute warped, diff and norm from pair and
+ *    flow with the forward's arithmetic (`bilinear` must be the forward's) and read only the gradient.  grad_flow has the bits of the
+ *    float32 backward entry point fed the widened pair, flow and gradient and the FLOAT32 forward's own output, rounded once.
+ *   pair, flow      : as the float32 entry points, elements of `dtype`
+ *   out / out_norm  : B x (3C+3) x H x W / B x 1 x H x W, fully written
+ *   grad_cat        : B x (3C+3) x H x W gradient of the concat (channels [0, 2C) are not read: the pair gets no gradient here)
+ *   grad_norm       : B x 1 x H x W
+ *   grad_flow       : B x 2 x H x W, fully written
+ * The pair's own gradient (a scatter: float32 atomics, or fixed point in the _det entry points) stays float32: widen, call the
+ * float32 entry points, round once.  Any dtype but FN2_F16 / FN2_BF16: FN2_EDTYPE.  Shapes, NULL tensors and div_flow are checked as
+ * by the float32 entry points, pointers for 2-byte alignment (FN2_EALIGN), before anything is launched.  C = 3 on maps with
+ * H >= 16, W >= 32, W % 8 == 0 and 16-byte aligned tensors takes the LDS-window kernels (eight pixels per lane, 16-byte loads and
+ * stores), everything else one lane per pixel; the results do not depend on which.  kernel_size 1.
+ * "The float32 entry point on the widened inputs" means on a contiguous, 16-byte aligned float32 copy.  This matters in one place: the
+ * float32 forward's LDS-window kernel (maps with H >= 16, W >= 32, W % 4 == 0) takes the norm's square root with the bare v_sqrt_f32
+ * (1 ulp), its one-lane kernel with the correctly rounded refinement, and the two differ in the last bit for a small share of sums.
+ * The 16-bit entry points use, on every path, the square root the float32 forward uses for the same shape. */
+int fn2_warp_diff_norm_cat_16(const void *pair, const void *flow, void *out, int dtype, float div_flow,
+                              int B, int C, int H, int W, int bilinear, void *stream);
+int fn2_warp_diff_norm_cat_backward_16(const void *pair, const void *flow, const void *grad_cat, void *grad_flow, int dtype,
+                                       float div_flow, int B, int C, int H, int W, int bilinear, void *stream);
+int fn2_warp_diff_norm_16(const void *pair, const void *flow, void *out_norm, int dtype, int B, int C, int H, int W, int bilinear,
+                          void *stream);
+int fn2_warp_diff_norm_backward_16(const void *pair, const void *flow, const void *grad_norm, void *grad_flow, int dtype,
+                                   int B, int C, int H, int W, int bilinear, void *stream);
 
 /* "Next" row N3: the training loss of FlowNet2 -- MultiScale with the L1 norm (losses.py:52-86) -- and
  * the EPE metric (losses.py:11-12) in one pass over the target flow instead of five AvgPool2d passes and ~35 launches.
