@@ -64,6 +64,8 @@ static int corr_forward_impl(const void *in1, const void *in2, void *out, int64_
     // f16x2: two-term f16 split done once per staged value, 3 MFMAs per block product (correlation_f16x2.hip)
     const bool f16x2_ok = corr_f16x2_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
                           aligned(in1, 16) && aligned(in2, 16) && aligned(out, 16) && (out_batch_stride % 4 == 0);
+    // the dense stride-1 kernels by name (fn2_debug.h; correct results): decided before anything is launched
+    if (debug_variant && algo == FN2_DEBUG_CORR_DENSE) return corr_forward_dense(in1, in2, out, dtype, p, s);
     if (debug_variant && algo >= 5000) {
         if (!f16x2_ok) return FN2_EUNSUPPORTED;
         return corr_forward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<float *>(out),
@@ -103,6 +105,13 @@ static int corr_forward_impl(const void *in1, const void *in2, void *out, int64_
         aligned(in1, 16) && aligned(in2, 16) && aligned(out, 16) && (out_batch_stride % 2 == 0)) {
         rc = corr_forward_mfma_f64(static_cast<const double *>(in1), static_cast<const double *>(in2), static_cast<double *>(out), p.out_bs,
                                    (double)p.slope, B, C, H, W, s);
+        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
+    }
+    // dense stride-1 cost volumes (correlation_dense.hip): the general kernel's bits, so AUTO may take them; FN2_CORR_DIRECT never
+    // does.  Maps with too few tiles to fill the chip stay on the general kernel, which is faster there (corr_dense_forward_pays)
+    if (algo == FN2_CORR_AUTO && corr_dense_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
+        corr_dense_forward_pays(p)) {
+        rc = corr_forward_dense(in1, in2, out, dtype, p, s);
         if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
     }
     return corr_forward_direct(in1, in2, out, dtype, p, s);
@@ -163,6 +172,7 @@ static int corr_backward_impl(const void *in1, const void *in2, const void *grad
     // f16x2: one-time two-term f16 split, gathered G operand (correlation_f16x2_bwd.hip)
     const bool f16x2_ok = corr_bwd_f16x2_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
                           aligned(in1, 16) && aligned(in2, 16) && aligned(grad_out, 16) && aligned(grad_in1, 16) && aligned(grad_in2, 16);
+    if (debug_variant && algo == FN2_DEBUG_CORR_DENSE) return corr_backward_dense(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);
     if (debug_variant && algo >= 6000) {
         if (!f16x2_ok) return FN2_EUNSUPPORTED;
         return corr_backward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<const float *>(grad_out),
@@ -200,6 +210,10 @@ static int corr_backward_impl(const void *in1, const void *in2, const void *grad
         aligned(in1, 16) && aligned(in2, 16) && aligned(grad_out, 16)) {
         rc = corr_backward_mfma_f64(static_cast<const double *>(in1), static_cast<const double *>(in2), static_cast<const double *>(grad_out),
                                     static_cast<double *>(grad_in1), static_cast<double *>(grad_in2), B, C, H, W, s);
+        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
+    }
+    if (algo == FN2_CORR_AUTO && corr_dense_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
+        rc = corr_backward_dense(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);
         if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
     }
     return corr_backward_direct(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);

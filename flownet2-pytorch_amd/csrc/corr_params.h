@@ -16,6 +16,15 @@ int corr_make_params(CorrP &p, int B, int C, int H, int W, int pad, int k, int m
 int corr_forward_direct(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s);
 int corr_backward_direct(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype,
                          const CorrP &p, hipStream_t s);
+
+// dense stride-1 cost volumes (PWC-Net: k = 1, s1 = s2 = 1, pad == md, 1 <= md <= 4; f32 / f16 / bf16; correlation_dense.hip): LDS-tiled
+// VALU kernels with the bits of corr_*_direct.  They decline (FN2_EUNSUPPORTED, nothing launched) outside that domain and for
+// shapes beyond their 32-bit offsets; p.out_bs and p.slope are honoured like in corr_forward_direct
+bool corr_dense_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
+bool corr_dense_forward_pays(const CorrP &p);   // enough workgroups for the dense forward to beat the general kernel (AUTO asks; the debug variant does not)
+int corr_forward_dense(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s);
+int corr_backward_dense(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype,
+                        const CorrP &p, hipStream_t s);
 bool corr_mfma_f32_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
 int corr_forward_mfma_f32(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H,
                           int W, int md, int tune, hipStream_t s);

@@ -17,20 +17,12 @@
 // are defined as 0 here (the CPU checker under tests/ defines them the same way).
 #include <type_traits>
 
+#include "corr_arith.h"
 #include "corr_params.h"
 
 namespace fn2 {
 
-
-template <typename T> struct Acc { typedef float type; };
-template <> struct Acc<double> { typedef double type; };
-
-// one product of the forward: in T (:124), except for bf16 (exact in fp32)
-template <typename T> __device__ __forceinline__ float fwd_prod(T a, T b)
-{
-    if constexpr (std::is_same<T, bf16_t>::value) return (float)a * (float)b;
-    else return (float)(T)(a * b);
-}
+// Acc<T> and fwd_prod<T> (one product of the forward) live in corr_arith.h, shared with correlation_dense.hip
 
 // ---------------------------------------------------------------- forward
 template <typename T>

@@ -6,9 +6,16 @@
 //                      5000 + v     correlation_f16x2.hip with profiling switches v (1 no MFMA, 2 no global loads,
 //                                   4 no stores, 8 no operand reads, 16 no split / LDS staging writes)
 //   backward variants: 100 + v      instantiations of correlation_mfma_bwd.hip
+//   both             : 9000         FN2_DEBUG_CORR_DENSE: the dense stride-1 kernels of correlation_dense.hip by name (kernel_size 1,
+//                                   stride1 = stride2 = 1, pad_size == max_displacement in 1 .. 4, float / half / bfloat16), or
+//                                   FN2_EUNSUPPORTED outside that domain, decided before anything is launched.  Unlike every other
+//                                   variant its results are correct: the bits of FN2_CORR_DIRECT, which is what FN2_CORR_AUTO runs
+//                                   there -- this value only makes the choice explicit for tests and benchmarks
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#define FN2_DEBUG_CORR_DENSE 9000
 
 #ifdef __cplusplus
 extern "C" {

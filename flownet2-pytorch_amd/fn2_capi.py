@@ -34,6 +34,10 @@ DEBUG_EXPORTS = ["fn2_debug_correlation_forward", "fn2_debug_correlation_backwar
                  "fn2_debug_resample2d_forward", "fn2_debug_resample2d_backward", "fn2_debug_stream_copy", "fn2_debug_mfma_probe",
                  "fn2_debug_xcc_census"]
 
+# the one debug variant whose results are correct: the dense stride-1 kernels (csrc/correlation_dense.hip) by name, for
+# correlation_forward / correlation_backward(..., algo=FN2_DEBUG_CORR_DENSE); FN2_EUNSUPPORTED outside their domain
+FN2_DEBUG_CORR_DENSE = 9000
+
 _lib = None
 _dbg = None
 

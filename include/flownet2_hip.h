@@ -77,6 +77,19 @@ enum {
     FN2_EUNSUPPORTED = -4 /* parameter combination the reference itself leaves undefined */
 };
 
+/* Dense stride-1 cost volumes under FN2_CORR_AUTO (PWC-Net, IRR-PWC, LiteFlowNet: kernel_size 1, stride1 1, stride2 1,
+ * pad_size == max_displacement == md, 1 <= md <= 4; float, half and bfloat16 tensors; any B, C, H, W, element-aligned
+ * pointers): forward (plain and fused) and backward run LDS-tiled kernels (csrc/correlation_dense.hip) whose every output
+ * element has the SAME BITS as FN2_CORR_DIRECT for the same call -- the same products, the same four partial sums and
+ * sequential backward sum in the same order, absent (not zero-multiplied) terms outside the image -- so the bounds given for
+ * FN2_CORR_DIRECT below hold for them unchanged.  (NaN results are NaN in both; their payloads are not specified.)
+ * What stays on the general kernel: md > 4, double tensors, shapes beyond the launcher's 32-bit offsets of one batch item,
+ * and the FORWARD of a small problem -- fewer than 192 tiles of 32 x 4 pixels over the whole batch (at B = 8: maps below
+ * 48 x 64) --, where the general kernel is measured faster (a tile's channels are walked serially by one workgroup;
+ * DESIGN.md 4.9).  The backward takes the tiled kernels at every size.
+ * No selector names these kernels and FN2_ABI_VERSION did not change with them: a caller cannot tell a library that has them
+ * from one that does not by its results, only by its speed; that is the point.  FN2_CORR_DIRECT keeps selecting the general
+ * kernel. */
 /* correlation algorithm selector for fn2_correlation_forward_ex */
 enum {
     FN2_CORR_AUTO = 0,    /* fastest kernel whose preconditions hold */
