@@ -45,6 +45,20 @@ bool corr_f16_bwd_applicable(int dtype, int C, int H, int W, int pad, int k, int
 int corr_backward_f16(int dtype, const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W,
                       hipStream_t s);
 
+// Neighbour row blocks of a backward task (FlowNetC's configuration: 4 centre lattice rows per row group rg, displacement radius dr
+// lattice rows, nu = ceil((2 dr + 4) / 4) blocks of 4 neighbour rows: block u holds lattice rows 4rg - dr + 4u .. +3 of a parity
+// lattice of HL rows).  A block is REAL iff one of its rows lies in [0, HL): 4rg - dr + 4u + 3 >= 0 and 4rg - dr + 4u <= HL - 1 (the
+// rule of correlation_mfma_bwd.hip); a block that is not contributes zeros only (its X rows do not exist) and is not walked.  The
+// range is never empty for a row group of the image (4rg <= HL - 1): the blocks that hold the centre rows themselves meet it.
+struct URange { int lo, hi; };
+__host__ __device__ constexpr URange bwd_u_range(int rg, int HL, int dr = 10, int nu = 6)
+{
+    const int lo = (dr - 4 * rg) >> 2, hi = (HL - 1 + dr - 4 * rg) >> 2;   // ceil((dr - 3 - 4rg) / 4), floor((HL - 1 + dr - 4rg) / 4)
+    return URange{lo < 0 ? 0 : lo, hi > nu - 1 ? nu - 1 : hi};
+}
+static_assert(bwd_u_range(0, 24).lo == 2 && bwd_u_range(1, 24).lo == 1 && bwd_u_range(2, 24).lo == 0 && bwd_u_range(3, 24).hi == 5 &&
+              bwd_u_range(4, 24).hi == 4 && bwd_u_range(5, 24).hi == 3 && bwd_u_range(0, 1).lo == 2 && bwd_u_range(0, 1).hi == 2, "real row blocks");
+
 void corr_f16x2_set_debug_buffer(void *p);
 void *corr_f16x2_get_debug_buffer();
 bool corr_bwd_f16x2_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);

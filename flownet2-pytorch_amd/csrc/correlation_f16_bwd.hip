@@ -4,8 +4,8 @@
 // The reference dispatches its backward kernels for at::Half too (correlation_cuda_kernel.cu:150-334, :460-554; it sums in
 // half there, :229 -- this kernel sums in fp32 like the general kernel and the oracle, the more accurate superset).  Half
 // tensors ARE f16 matrix operands: the banded contraction of correlation_f16x2_bwd.hip (read its header first: task = (gradient,
-// batch item, y parity, 4 centre rows, 64 channels), the workgroup walks the 6 neighbour row blocks u, 4 staging + 8 matrix
-// waves) with everything the fp32 operands needed removed:
+// batch item, y parity, 4 centre rows, 64 channels), the workgroup walks the neighbour row blocks u that meet the image -- 4 to 6
+// of the 6 at 48 rows --, 4 staging + 8 matrix waves) with everything the fp32 operands needed removed:
 //   - no split, no block scale: ONE v_mfma_f32_16x16x32_f16 per (centre block, block pair, channel tile) instead of three
 //     (24 per matrix wave and u instead of 72); products of two halfs are exact in fp32;
 //   - X operand (in2 / in1): one 16-byte load = 8 pixels = the two parity chunks after four v_perm_b32 (as correlation_f16_fwd.hip),
@@ -146,6 +146,9 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
         k.flip = __builtin_amdgcn_readfirstlane(k.flip);
         return k;
     };
+    // the neighbour row blocks a task walks: those that meet the image (bwd_u_range, corr_params.h), in ascending u -- the others
+    // hold zeros only
+    auto task_u = [&](const Task &k) -> URange { return bwd_u_range(k.rg, HL, DR, NU); };
 
     // ---- write-out of the epilogue image (all waves): 256 rows (channel, centre row) of 64 floats -> half rows of 128 B
     float *Es = reinterpret_cast<float *>(smem + X_OFS);
@@ -300,37 +303,63 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
         XSet XA0, XA1, XB0, XB1;
         GSet GS;
         int t = (int)xcd_remap(blockIdx.x, gridDim.x);
+        const int gs = (int)gridDim.x;
         if (t < ntasks) {
+            // the first two steps: the first task's first real block and the step after it (the task's next block, or -- a task of
+            // one block -- the first block of the workgroup's next task)
             const Task tk = get_task(t);
-            g_issue(GS, tk, 0, true);
-            x_issue(XA0, tk, 0, 0, true);
-            x_issue(XA1, tk, 0, 1, true);
+            const URange ur = task_u(tk);
+            const bool more = ur.lo < ur.hi, has_next = t + gs < ntasks;
+            const Task t1 = more ? tk : get_task(has_next ? t + gs : t);
+            g_issue(GS, tk, ur.lo, true);
+            x_issue(XA0, tk, ur.lo, 0, true);
+            x_issue(XA1, tk, ur.lo, 1, true);
             g_write(GS, tk);
-            g_issue(GS, tk, 1, true);
+            g_issue(GS, t1, more ? ur.lo + 1 : task_u(t1).lo, more || has_next);
         }
-        __syncthreads();                                       // (A) G(0) of the first task complete
-        for (; t < ntasks; t += gridDim.x) {
+        __syncthreads();                                       // (A) the first G image of the first task complete
+        for (; t < ntasks; t += gs) {
             const Task tk = get_task(t);
-            const bool has_next = t + (int)gridDim.x < ntasks;
-            const Task tn = get_task(has_next ? t + (int)gridDim.x : t);
-            auto one_u = [&](int u, XSet &C0, XSet &C1, XSet &N0, XSet &N1) {
+            const bool has_next = t + gs < ntasks, has_next2 = t + 2 * gs < ntasks;
+            const Task tn = get_task(has_next ? t + gs : t);
+            const Task tnn = get_task(has_next2 ? t + 2 * gs : t);
+            const URange ur = task_u(tk), un = task_u(tn);
+            const int unn_lo = task_u(tnn).lo;
+            // one step (a real block u of the task); returns whether it was the task's last
+            auto one_u = [&](int u, XSet &C0, XSet &C1, XSet &N0, XSet &N1) -> bool {
+                // The workgroup's steps are one sequence across its tasks: after block u comes u + 1, after the task's last real
+                // block the first real block of the next task.  (t1, u1) is the next step, (t2, u2) the one after it -- which is in
+                // the task after next where the next task has a single block.
+                const bool more = u < ur.hi;
+                const Task t1 = pick(more, tk, tn);
+                const int u1 = more ? u + 1 : un.lo;
+                const bool v1 = more || has_next;
+                const bool more2 = more ? u + 1 < ur.hi : un.lo < un.hi;           // the step after the next stays in the next one's task
+                const Task t2 = pick(more2, t1, pick(more, tn, tnn));
+                const int u2 = more2 ? u1 + 1 : (more ? un.lo : unn_lo);
+                const bool v2 = more2 ? v1 : (more ? has_next : has_next2);
                 // phase 1 (the matrix waves gather the G operands of u): request the next X chunks, write both X chunks of u
-                const bool more = u + 1 < NU, more2 = u + 2 < NU;
-                const Task t1 = pick(more, tk, tn), t2 = pick(more2, tk, tn);      // the tasks of the next step and the one after
-                x_issue(N0, t1, more ? u + 1 : 0, 0, more || has_next);
-                x_issue(N1, t1, more ? u + 1 : 0, 1, more || has_next);
+                x_issue(N0, t1, u1, 0, v1);
+                x_issue(N1, t1, u1, 1, v1);
                 x_write(C0, smem + X_OFS);
                 x_write(C1, smem + X_OFS + XBUF);
                 __syncthreads();                               // (B) the G image is free, the X chunks complete
                 // phase 2 (all MFMAs of u): convert and write the NEXT step's G image (its rows were requested a whole step
                 // ago), then request the rows of the step after it into the same registers
-                if (more || has_next) g_write(GS, t1);
-                g_issue(GS, t2, more2 ? u + 2 : u + 2 - NU, more2 || has_next);
+                if (v1) g_write(GS, t1);
+                g_issue(GS, t2, u2, v2);
                 __syncthreads();                               // (A') the X buffers are free, the next G image complete
+                return !more;
             };
-            for (int u = 0; u < NU; u += 2) {
-                one_u(u, XA0, XA1, XB0, XB1);
-                one_u(u + 1, XB0, XB1, XA0, XA1);
+            // The X register sets alternate statically (loop unrolled by two).  A task with an odd number of steps ends with the next
+            // task's first chunks requested into XB: they are handed over to XA (32 v_mov per staging wave, while the matrix waves
+            // scatter their accumulators) so that every task starts on XA.
+            for (int u = ur.lo;; u += 2) {
+                if (one_u(u, XA0, XA1, XB0, XB1)) {
+                    XA0 = XB0; XA1 = XB1;
+                    break;
+                }
+                if (one_u(u + 1, XB0, XB1, XA0, XA1)) break;
             }
             __syncthreads();                                   // epilogue image (over the X buffers) complete
             store_rows(tk);
@@ -446,11 +475,14 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
             default: mma(std::integral_constant<int, 3>{}); break;
             }
         };
-        for (int u = 0; u < NU; ++u) {
+        // one step per real neighbour row block of the task (the staging waves walk the same range: the barriers pair up); neither
+        // the gather nor the MFMAs depend on u
+        const URange ur = task_u(tk);
+        for (int u = ur.lo; u <= ur.hi; ++u) {
             gather_d();                                        // phase 1
             __syncthreads();                                   // (B) both X chunks of u complete, the G image is free
             mma_d();                                           // phase 2
-            __syncthreads();                                   // (A') the X buffers are free; G(u+1) complete
+            __syncthreads();                                   // (A') the X buffers are free; the next G image complete
         }
         // epilogue: D[row = channel 4q + r][col = pixel i] -> Es[c][ai][x], 16-byte slots rotated by 8 ai + 32 ((c>>2)&1)
         auto scatter = [&](auto role_c) {
@@ -486,7 +518,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
         store_rows(tk);
         __syncthreads();
     };
-    __syncthreads();                                           // (A) G(0) of the first task complete
+    __syncthreads();                                           // (A) the first G image of the first task complete
     for (int t = (int)xcd_remap(blockIdx.x, gridDim.x); t < ntasks; t += gridDim.x) {
         const Task tk = get_task(t);
         if (tk.flip) run_task(tk, std::integral_constant<int, 1>{});

@@ -14,8 +14,11 @@
 // pixels of a 4x4 block.
 //
 // Task = (FLIP, n, y parity, row group rg of 4 centre lattice rows, group of 64 channels); the workgroup loops over the
-// 6 neighbour row blocks u itself (rows 4rg - 10 + 4u .. +3): the sum over neighbours stays in registers, no atomics,
-// deterministic.  Per u:
+// neighbour row blocks u itself (rows 4rg - 10 + 4u .. +3; u in 0 .. 5): the sum over neighbours stays in registers, no atomics,
+// deterministic.  Only the blocks that meet the image are walked (bwd_u_range, corr_params.h: u_lo .. u_hi, ascending; 4 to 6 of
+// the 6 at 48 rows, one at H = 2): a block outside it holds zeros only, so leaving it out removes additions of exact zeros and
+// keeps the order of the other terms.  The last step of a task prefetches the first real block of the workgroup's next task.
+// Per u:
 //   G image   the 16 (centre row ai, neighbour row bi) combinations x 21 displacement columns x 64 pixels of gO that the
 //             pair (rg, u) touches -- the forward's output tile -- as raw fp32 rows [ai][ti][bi][x] in LDS, copied by LDS-DMA
 //             (buffer_load_dwordx4 ... lds: the four rows bi of one (ai, ti) = 1 KB per instruction; no VGPRs, no VALU, no
@@ -30,7 +33,7 @@
 //   X tile    4 neighbour rows x 64 pixels x 32 channels per chunk, split once while staging, in the forward kernel's LDS image
 //             (8-byte chunks of 4 lattice columns, [term][parity][channel][...]) with the 16-byte units of a channel ordered
 //             (block pair, row pair, block): the X operand of (channel tile, block pair) is two plain ds_read_b128 (hi, lo).
-// 12 waves per workgroup, 3 per SIMD (168-register budget: 158 used, no scratch), specialised: waves 0-3 stage (the G DMA,
+// 12 waves per workgroup, 3 per SIMD (168-register budget: 161 used, no scratch), specialised: waves 0-3 stage (the G DMA,
 // buffer loads of X whose range check returns zeros outside the image, X split, LDS writes), waves 4-11 gather and run the
 // MFMAs: matrix wave w takes x parity w&1 and the centre column blocks of role w>>1 ({0,3},{1,2},{4,7},{5,6}: 6 (block, pair)
 // products each) x 4 channel tiles.  MFMA and VALU instructions of one SIMD do not overlap (scripts/ubench/mfma_valu_overlap),
@@ -222,6 +225,11 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
             for (int i = 0; i < 16; ++i) d[i] = ts[i];
         }
     };
+    // the four stamps of step si = 0, 1 of a task (constant slots: ts stays in registers)
+    auto stamp_u = [&](int si, int k) __attribute__((always_inline)) {
+        if (si == 0) stamp(4 + k);
+        else if (si == 1) stamp(8 + k);
+    };
     stamp(0);
 
     struct Task { int flip, n, py, rg, cg; };
@@ -247,6 +255,15 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
         k.py = __builtin_amdgcn_readfirstlane(k.py); k.n = __builtin_amdgcn_readfirstlane(k.n);
         k.flip = __builtin_amdgcn_readfirstlane(k.flip);
         return k;
+    };
+    // The neighbour row blocks a task walks: the real ones (bwd_u_range, corr_params.h), in ascending u.  A block outside the image
+    // holds zeros only -- skipping it removes additions of exact zeros and leaves the order of the remaining terms as it was.
+    auto task_u = [&](const Task &k) -> URange {
+        URange r = bwd_u_range(k.rg, HL, DR, NU);
+#ifdef FN2_ABL_EVENU   // A/B: an odd count is extended by one adjacent empty block (no register-set hand-over in the staging waves)
+        if (!((r.hi - r.lo) & 1)) { if (r.lo > 0) --r.lo; else ++r.hi; }
+#endif
+        return r;
     };
 
     // ---- write-out of the epilogue image (all waves): 256 rows (channel, centre row) of 64 floats, 4 rows per instruction
@@ -454,6 +471,11 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
                 if (ln == 0) scl_k[1] = kg;
             }
         };
+        auto pick = [](bool c, const Task &a, const Task &b) {   // scalar selects, field by field
+            Task r;
+            r.flip = c ? a.flip : b.flip; r.n = c ? a.n : b.n; r.py = c ? a.py : b.py; r.rg = c ? a.rg : b.rg; r.cg = c ? a.cg : b.cg;
+            return r;
+        };
         XSet XA0, XA1, XB0, XB1;
         int t = (int)xcd_remap(blockIdx.x, gridDim.x);
         Samp SM;
@@ -461,17 +483,18 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
         int it = 0;                                            // tasks done by this workgroup: parity selects the half of scl_sx
         if (t < ntasks) {
             const Task tk = get_task(t);
+            const int u0 = task_u(tk).lo;
             sample_issue(tk, SM);
-            x_issue(XA0, tk, 0, 0);
-            x_issue(XA1, tk, 0, 1);
-            g_dma(tk, 0);
+            x_issue(XA0, tk, u0, 0);
+            x_issue(XA1, tk, u0, 1);
+            g_dma(tk, u0);
             stamp(1);
             dma_wait();
             stamp(2);
             sample_scales(SM, kx_n, kg_n);
             publish(0, kx_n, kg_n);
         }
-        __syncthreads();                                       // (A) G(0) complete, the first task's exponents published
+        __syncthreads();                                       // (A) the first G image complete, the first task's exponents published
         stamp(3);
         for (; t < ntasks; t += gridDim.x) {
             const Task tk = get_task(t);
@@ -479,15 +502,23 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
             const Task tn = get_task(has_next ? t + (int)gridDim.x : t);
             const bool first = t < (int)gridDim.x;
             const int kg_cur = kg_n, par = it & 1;
-            auto one_u = [&](int u, XSet &C0, XSet &C1, XSet &N0, XSet &N1) {
+            const URange ur = task_u(tk);
+            const int un_lo = task_u(tn).lo;                   // where the next task starts: what the last u of this one prefetches
+            // step i = u - ur.lo of the task; returns whether it was the last one
+            auto one_u = [&](int u, XSet &C0, XSet &C1, XSet &N0, XSet &N1) -> bool {
+                const bool last = u == ur.hi;
+                const Task t1 = pick(last, tn, tk);            // the step after this one: block u + 1, or the next task's first block
+                const int u1 = last ? un_lo : u + 1;
+                const int si = u - ur.lo;                      // (profiling: the stamps are those of the first two EXECUTED steps)
                 // the scale of item k of chunk ch (channel s_ch + 8 (k + 4 ch)) is read from the table one item ahead of its use: all
                 // eight of them in registers across the phase do not fit the staging waves' budget (168 with four X sets in flight)
                 const float *sxp = &scl_sx[par][8 * s_ch];
                 // phase 1 (the matrix waves gather the G operands of u): request the next X chunks, write both X chunks of u
                 // (all loads first: interleaving them with the items of x_write measured 4 us slower)
                 float sc = sxp[0];
-                if (u + 1 < NU) { x_issue(N0, tk, u + 1, 0); x_issue(N1, tk, u + 1, 1); }
-                else if (has_next) { x_issue(N0, tn, 0, 0); x_issue(N1, tn, 0, 1); }
+                // (unconditional: after the last step of the workgroup's last task t1 is that task again and the rows are fetched for
+                // nothing, 16 loads per lane once per launch -- a set that is written on every path keeps the other one out of scratch)
+                x_issue(N0, t1, u1, 0); x_issue(N1, t1, u1, 1);
 #pragma unroll
                 for (int k = 0; k < 2 * XK; ++k) {
                     const float nx = sxp[k + 1 < 2 * XK ? k + 1 : k];
@@ -495,20 +526,28 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
                     else x_write1(C1, smem + X_OFS + XBUF, k - XK, sc);
                     sc = nx;
                 }
-                if (first && u < 2) stamp(4 + 4 * u);
+                if (first) stamp_u(si, 0);
                 __syncthreads();                               // (B) the G image is free, the X chunks complete
-                if (first && u < 2) stamp(5 + 4 * u);
-                // phase 2 (all MFMAs of u): G(u+1), or G(0) of the next task, by DMA (and the next task's operand sample, ahead of it)
-                if (u + 1 < NU) g_dma(tk, u + 1);
-                else if (has_next) { sample_issue(tn, SM); g_dma(tn, 0); }
+                if (first) stamp_u(si, 1);
+                // phase 2 (all MFMAs of u): G(u+1), or the first G of the next task, by DMA (and the next task's operand sample, ahead
+                // of it)
+                if (last && has_next) sample_issue(tn, SM);
+                if (!last || has_next) g_dma(t1, u1);
                 dma_wait();
-                if (first && u < 2) stamp(6 + 4 * u);
+                if (first) stamp_u(si, 2);
                 __syncthreads();                               // (A') the X buffers are free, the next G image complete
-                if (first && u < 2) stamp(7 + 4 * u);
+                if (first) stamp_u(si, 3);
+                return last;
             };
-            for (int u = 0; u < NU; u += 2) {
-                one_u(u, XA0, XA1, XB0, XB1);
-                one_u(u + 1, XB0, XB1, XA0, XA1);
+            // The two register sets alternate statically (loop unrolled by two).  A task with an odd number of steps ends with the
+            // next task's first chunks in flight in XB: they are handed over to XA (64 v_mov per staging wave, while the matrix waves
+            // scatter their accumulators; the loads landed before the dma_wait of the last step) so that every task starts on XA.
+            for (int u = ur.lo;; u += 2) {
+                if (one_u(u, XA0, XA1, XB0, XB1)) {
+                    XA0 = XB0; XA1 = XB1;
+                    break;
+                }
+                if (one_u(u + 1, XB0, XB1, XA0, XA1)) break;
             }
             // while the matrix waves scatter their accumulators: the next task's scale exponents (every wave has read the current
             // ones: the matrix waves do at the top of the task)
@@ -534,6 +573,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
     const int role = __builtin_amdgcn_readfirstlane(w8 >> 1);
 
     int itm = 0;   // tasks done by this workgroup (parity: which half of scl_sx holds the current task's X exponents)
+    int steps_run = 0;   // profiling (VAR 64): steps this workgroup executed, all its tasks together
     auto run_task = [&](const Task &tk, auto flipc, bool first) {
         constexpr int FLIP = decltype(flipc)::value;
         const int kg_cur = to_sgpr(scl_k[1]);                   // published before the barrier this wave just passed
@@ -694,16 +734,21 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
             }
         };
 
-        for (int u = 0; u < NU; ++u) {
+        // one step per real neighbour row block of the task (the staging waves walk the same range: the barriers pair up); neither
+        // the gather nor the MFMAs depend on u -- which rows the G image and the X chunks hold is the staging waves' business
+        const URange ur = task_u(tk);
+        const int nsteps = ur.hi - ur.lo + 1;
+        for (int si = 0; si < nsteps; ++si) {
             gather_d();                                        // phase 1
-            if (first && u < 2) stamp(4 + 4 * u);
+            if (first) stamp_u(si, 0);
             __syncthreads();                                   // (B) both X chunks of u complete, the G image is free
-            if (first && u < 2) stamp(5 + 4 * u);
+            if (first) stamp_u(si, 1);
             mma_d();                                           // phase 2
-            if (first && u < 2) stamp(6 + 4 * u);
-            __syncthreads();                                   // (A') the X buffers are free; G(u+1) complete
-            if (first && u < 2) stamp(7 + 4 * u);
+            if (first) stamp_u(si, 2);
+            __syncthreads();                                   // (A') the X buffers are free; the next G image complete
+            if (first) stamp_u(si, 3);
         }
+        if (VAR & 64) steps_run += nsteps;
         if (first) stamp(12);
 
         // epilogue: D[row = channel 4q + r][col = pixel i] -> Es[c][ai][x], 16-byte slots rotated by 8 ai + 32 ((c>>2)&1)
@@ -735,7 +780,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
         __syncthreads();
         if (first) stamp(14);
     };
-    __syncthreads();                                           // (A) G(0) of the first task complete, its scale exponents published
+    __syncthreads();                                           // (A) the first G image of the first task complete, its scale exponents published
     stamp(3);
     for (int t = (int)xcd_remap(blockIdx.x, gridDim.x); t < ntasks; t += gridDim.x, ++itm) {
         const Task tk = get_task(t);
@@ -744,6 +789,9 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
         else run_task(tk, std::integral_constant<int, 0>{}, first);
     }
     stamp(15);
+    // profiling: slots 1 and 2 are stamped by the staging waves only -- the matrix wave's slot 1 carries the workgroup's step count
+    // (a test reads back what ran; scripts/corr_micro.py takes it out of the timeline)
+    if (VAR & 64) ts[1] = (unsigned long long)steps_run;
     dump();
 }
 

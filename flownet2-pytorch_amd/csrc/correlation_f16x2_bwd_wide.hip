@@ -5,7 +5,8 @@
 // narrow kernel; read its header first.  What the width adds: on a parity lattice a centre column block a (4 lattice columns =
 // 8 pixels) has neighbours in the column blocks a-3 .. a+3.  A task now owns a CENTRE WINDOW of 8 column blocks (64 pixels,
 // window index xw) of its 4 centre rows and walks the neighbour blocks 8xw-3 .. 8xw+12 in two PASSES of 8 blocks (64 pixels:
-// exactly the X chunk and the G image of the narrow kernel), each pass over the 6 neighbour row blocks u:
+// exactly the X chunk and the G image of the narrow kernel), each pass over the neighbour row blocks u that meet the image
+// (bwd_u_range, corr_params.h: as the narrow kernel -- 36 of the 42 (row group, u) pairs at 56 rows):
 //     pass 0: neighbour blocks 8xw-3 .. 8xw+4        pass 1: 8xw+5 .. 8xw+12 (skipped when it lies right of the image)
 // The sums of both passes stay in the same accumulators (no atomics, deterministic).  The centre blocks of a matrix wave are
 // paired {0,7} {1,6} {2,5} {3,4}: every wave then has 5 (centre block, neighbour block pair) products in pass 0 and 3 in pass 1
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
     const bool pow2 = (p.C & (p.C - 1)) == 0;
     const int lgC = pow2 ? 31 - __builtin_clz((unsigned)p.C) : 0;
 
-    struct Task { int flip, n, py, rg, xw, cg, nv; };
+    struct Task { int flip, n, py, rg, xw, cg, nv, ulo, cnt; };
     auto get_task = [&](int t) -> Task {
         Task k;
         k.cg = t % p.NCGR; t /= p.NCGR;
@@ -160,10 +161,16 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
         k.xw = __builtin_amdgcn_readfirstlane(k.xw);
         k.py = __builtin_amdgcn_readfirstlane(k.py); k.n = __builtin_amdgcn_readfirstlane(k.n);
         k.flip = __builtin_amdgcn_readfirstlane(k.flip);
-        k.nv = (WPX * k.xw + 8 * PO(1) < p.W) ? 2 * NU : NU;   // (pass, u) steps: pass 1 only if its first block is inside the image
+        // (pass, u) steps: the cnt neighbour row blocks ulo .. ulo + cnt - 1 that meet the image (bwd_u_range, corr_params.h; the
+        // others hold zeros only), once per pass; pass 1 only if its first block is inside the image
+        const URange ur = bwd_u_range(k.rg, HL, DR, NU);
+        k.ulo = ur.lo; k.cnt = ur.hi - ur.lo + 1;
+        k.nv = (WPX * k.xw + 8 * PO(1) < p.W) ? 2 * k.cnt : k.cnt;
         return k;
     };
-    // first pixel of the neighbour window of step v (pass v / NU)
+    // step s = 0 .. nv - 1 of a task -> v = NU pass + u
+    auto v_of = [&](const Task &k, int s) { return s >= k.cnt ? NU + k.ulo + s - k.cnt : k.ulo + s; };
+    // first pixel of the neighbour window of v (pass v / NU)
     auto nbr_x0 = [&](const Task &tk, int v) { return WPX * tk.xw + 8 * (v >= NU ? PO(1) : PO(0)); };
 
     // ---- write-out of the epilogue image (all waves): 256 rows (channel, centre row) of 64 floats, 4 rows per instruction
@@ -334,6 +341,12 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
                 if (ln == 0) scl_k[1] = kg;
             }
         };
+        auto pick = [](bool c, const Task &a, const Task &b) {   // scalar selects, field by field
+            Task r;
+            r.flip = c ? a.flip : b.flip; r.n = c ? a.n : b.n; r.py = c ? a.py : b.py; r.rg = c ? a.rg : b.rg; r.xw = c ? a.xw : b.xw;
+            r.cg = c ? a.cg : b.cg; r.nv = c ? a.nv : b.nv; r.ulo = c ? a.ulo : b.ulo; r.cnt = c ? a.cnt : b.cnt;
+            return r;
+        };
         XSet XA0, XA1, XB0, XB1;
         int t = (int)xcd_remap(blockIdx.x, gridDim.x);
         Samp SM;
@@ -342,26 +355,31 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
         if (t < ntasks) {
             const Task tk = get_task(t);
             sample_issue(tk, SM);
-            x_issue(XA0, tk, 0, 0);
-            x_issue(XA1, tk, 0, 1);
-            g_dma(tk, 0);
+            x_issue(XA0, tk, tk.ulo, 0);
+            x_issue(XA1, tk, tk.ulo, 1);
+            g_dma(tk, tk.ulo);
             dma_wait();
             sample_scales(SM, kx_n, kg_n);
             publish(0, kx_n, kg_n);
         }
-        __syncthreads();                                       // (A) G(0) complete, the first task's exponents published
+        __syncthreads();                                       // (A) the first G image complete, the first task's exponents published
         for (; t < ntasks; t += gridDim.x) {
             const Task tk = get_task(t);
             const bool has_next = t + (int)gridDim.x < ntasks;
             const Task tn = get_task(has_next ? t + (int)gridDim.x : t);
             const int kg_cur = kg_n, par = it & 1;
-            auto one_v = [&](int v, XSet &C0, XSet &C1, XSet &N0, XSet &N1) {
-                // phase 1 (the matrix waves gather the G operands of v): request the next X chunks, write both X chunks of v
+            // step s of the task; returns whether it was the last one
+            auto one_v = [&](int s, XSet &C0, XSet &C1, XSet &N0, XSet &N1) -> bool {
+                const bool last = s + 1 == tk.nv;
+                const Task t1 = pick(last, tn, tk);            // the step after this one: the task's next, or the next task's first
+                const int v1 = last ? tn.ulo : v_of(tk, s + 1);
+                // phase 1 (the matrix waves gather the G operands of the step): request the next X chunks, write both X chunks of it
+                // (unconditional: after the workgroup's last step t1 is its last task again and the rows are fetched for nothing,
+                // once per launch -- a set that is written on every path keeps the other one out of scratch)
                 int l5 = lane_now();
                 const float *sxp = &scl_sx[par][8 * (2 * w8 + (l5 >> 5))];   // the scales of the lane's eight channels, read one item ahead
                 float sc = sxp[0];
-                if (v + 1 < tk.nv) { x_issue(N0, tk, v + 1, 0); x_issue(N1, tk, v + 1, 1); }
-                else if (has_next) { x_issue(N0, tn, 0, 0); x_issue(N1, tn, 0, 1); }
+                x_issue(N0, t1, v1, 0); x_issue(N1, t1, v1, 1);
                 const int w_ofs = x_ofs();
 #pragma unroll
                 for (int k = 0; k < 2 * XK; ++k) {
@@ -371,15 +389,22 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
                     sc = nx;
                 }
                 __syncthreads();                               // (B) the G image is free, the X chunks complete
-                // phase 2 (all MFMAs of v): the next G image by DMA (and the next task's operand sample, ahead of it)
-                if (v + 1 < tk.nv) g_dma(tk, v + 1);
-                else if (has_next) { sample_issue(tn, SM); g_dma(tn, 0); }
+                // phase 2 (all MFMAs of the step): the next G image by DMA (and the next task's operand sample, ahead of it)
+                if (last && has_next) sample_issue(tn, SM);
+                if (!last || has_next) g_dma(t1, v1);
                 dma_wait();
                 __syncthreads();                               // (A') the X buffers are free, the next G image complete
+                return last;
             };
-            for (int v = 0; v < tk.nv; v += 2) {
-                one_v(v, XA0, XA1, XB0, XB1);
-                one_v(v + 1, XB0, XB1, XA0, XA1);
+            // The two register sets alternate statically (loop unrolled by two).  A task with an odd number of steps (one pass over an
+            // odd number of real blocks) ends with the next task's first chunks in XB: they are handed over to XA (64 v_mov per staging
+            // wave, while the matrix waves scatter; the loads landed before the dma_wait of the last step): every task starts on XA.
+            for (int s = 0;; s += 2) {
+                if (one_v(s, XA0, XA1, XB0, XB1)) {
+                    XA0 = XB0; XA1 = XB1;
+                    break;
+                }
+                if (one_v(s + 1, XB0, XB1, XA0, XA1)) break;
             }
             if (has_next) { sample_scales(SM, kx_n, kg_n); publish(par ^ 1, kx_n, kg_n); }
             __syncthreads();                                   // epilogue image (over the X buffers) complete
@@ -519,7 +544,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
             }
         };
         auto one_pass = [&](auto ps_c) {
-            for (int u = 0; u < NU; ++u) {
+            for (int u = 0; u < tk.cnt; ++u) {                     // the real row blocks: neither the gather nor the MFMAs depend on u
                 gather_d(ps_c);                                    // phase 1
                 __syncthreads();                                   // (B) both X chunks of the step complete, the G image is free
                 mma_d(ps_c);                                       // phase 2
@@ -527,7 +552,7 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
             }
         };
         one_pass(std::integral_constant<int, 0>{});
-        if (tk.nv > NU) one_pass(std::integral_constant<int, 1>{});
+        if (tk.nv > tk.cnt) one_pass(std::integral_constant<int, 1>{});
 
         // epilogue: D[row = channel 4q + r][col = pixel i] -> Es[c][ai][x], 16-byte slots rotated by 8 ai + 32 ((c>>2)&1)
         auto scatter = [&](auto role_c) {

@@ -124,7 +124,10 @@ if a.bwd:
                 print("   wave", w, [int(v) - t0 if v > 0 else None for v in st[w, :7]])
         if 6000 <= algo < 8000 and ((algo - 6000) & 64):   # f16x2 backward timeline of each workgroup's first task
             torch.cuda.synchronize()
-            st = dbg.cpu().view(256, 2, 16)
+            st = dbg.cpu().view(256, 2, 16).clone()
+            steps = st[:, 1, 1].clone()   # the matrix wave's slot 1 is no stamp: the (real) row-block steps the workgroup executed
+            st[:, 1, 1] = 0
+            print("   row-block steps per workgroup: min %d  max %d  total %d" % (int(steps.min()), int(steps.max()), int(steps.sum())))
             base = st[:, :, 0].min(dim=1, keepdim=True).values.unsqueeze(2)
             zero = st == 0
             st = (st - base).double()
