@@ -77,6 +77,7 @@ __global__ __launch_bounds__(256) void resample_fwd_kernel(const float *__restri
         }
         long o00[PX], o01[PX], o10[PX], o11[PX];
         double w00[PX], w01[PX], w10[PX], w11[PX];
+        // corners and weights written out: warp_fwd_corners / bilinear_weights here change the kernel's code
 #pragma unroll
         for (int i = 0; i < PX; ++i) {
             const float xf = (float)(x0 + i) + dx[i], yf = (float)y + dy[i];
@@ -114,16 +115,9 @@ __global__ __launch_bounds__(256) void resample_fwd_kernel(const float *__restri
             float v[PX];
 #pragma unroll
             for (int i = 0; i < PX; ++i) {
-                if (bilinear) {
-                    float val = 0.0f;
-                    val = val + (float)(w00[i] * (double)ic[o00[i]]);
-                    val = val + (float)(w01[i] * (double)ic[o01[i]]);
-                    val = val + (float)(w10[i] * (double)ic[o10[i]]);
-                    val = val + (float)(w11[i] * (double)ic[o11[i]]);
-                    v[i] = val;
-                } else {
-                    v[i] = ic[o00[i]];
-                }
+                const BilinearW w{w00[i], w01[i], w10[i], w11[i]};
+                if (bilinear) v[i] = bilinear_sample(w, ic[o00[i]], ic[o01[i]], ic[o10[i]], ic[o11[i]]);
+                else v[i] = ic[o00[i]];
             }
             if constexpr (PX == 4) {
                 f4 r = {v[0], v[1], v[2], v[3]};
@@ -158,13 +152,12 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const float *__restri
         const int b = (int)(row / H);
         const long p = (long)y * W + x;
         const float dx = flow[(long)b * 2 * HW + p], dy = flow[(long)b * 2 * HW + HW + p];
-        const float xf = (float)x + dx, yf = (float)y + dy;
-        const float fx = floorf(xf), fy = floorf(yf);
-        const int ixL = f2i_sat(fx), ixR = f2i_sat(fx + 1.0f), iyT = f2i_sat(fy), iyB = f2i_sat(fy + 1.0f);
+        int ixL, ixR, iyT, iyB;
+        float alpha, beta, fa, fb;
+        warp_bwd_pos(x, y, dx, dy, ixL, ixR, iyT, iyB, alpha, beta, fa, fb);
 
         // ---- grad_img: weights use truncation, alpha = xf - int(xf) (:105-106); corners clamped
         //      with the INPUT1 dims (:108-114); all float math (:118-121).
-        const float alpha = xf - (float)f2i_sat(xf), beta = yf - (float)f2i_sat(yf);
         const int sxL = clampi(ixL, 0, Wi - 1), sxR = clampi(ixR, 0, Wi - 1);
         const int syT = clampi(iyT, 0, Hi - 1), syB = clampi(iyB, 0, Hi - 1);
         const float s00 = (1 - alpha) * (1 - beta), s01 = alpha * (1 - beta);
@@ -173,8 +166,7 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const float *__restri
         // ---- grad_flow: corners clamped with the FLOW dims (:163-166) (then to the image, defensive)
         const int gxL = clampi(clampi(ixL, 0, W - 1), 0, Wi - 1), gxR = clampi(clampi(ixR, 0, W - 1), 0, Wi - 1);
         const int gyT = clampi(clampi(iyT, 0, H - 1), 0, Hi - 1), gyB = clampi(clampi(iyB, 0, H - 1), 0, Hi - 1);
-        const float gam_y = 1 - (xf - fx); // c == 1 branch: "gamma = 1 - (xf - floor(xf))" (:169)
-        const float gam_x = 1 - (yf - fy); // c == 0 branch (:182)
+        const float gam_y = 1 - fa, gam_x = 1 - fb;   // (:169, :182)
         float out_dx = 0.0f, out_dy = 0.0f;
 
         for (int ch = 0; ch < C; ++ch) {
@@ -199,16 +191,7 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const float *__restri
             const float *I = img + (long)b * is.b + (long)ch * is.c;
             const float iTL = I[gyT * is.h + gxL * is.w], iTR = I[gyT * is.h + gxR * is.w];
             const float iBL = I[gyB * is.h + gxL * is.w], iBR = I[gyB * is.h + gxR * is.w];
-            // d/d(dy)  (:172-177)
-            out_dy = out_dy + (gam_y * go) * iBL;
-            out_dy = out_dy - (gam_y * go) * iTL;
-            out_dy = out_dy + ((1 - gam_y) * go) * iBR;
-            out_dy = out_dy - ((1 - gam_y) * go) * iTR;
-            // d/d(dx)  (:185-190)
-            out_dx = out_dx + (gam_x * go) * iTR;
-            out_dx = out_dx - (gam_x * go) * iTL;
-            out_dx = out_dx + ((1 - gam_x) * go) * iBR;
-            out_dx = out_dx - ((1 - gam_x) * go) * iBL;
+            flow_grad_terms(out_dx, out_dy, gam_x, gam_y, go, iTL, iTR, iBL, iBR);
         }
         gflow[(long)b * 2 * HW + p] = out_dx;
         gflow[(long)b * 2 * HW + HW + p] = out_dy;
@@ -234,20 +217,21 @@ __global__ __launch_bounds__(256) void resample_fwd_ks_kernel(const float *__res
         const int b = (int)(row / H);
         const long p = (long)y * W + x;
         const float dx = flow[(long)b * 2 * HW + p], dy = flow[(long)b * 2 * HW + HW + p];
-        const float xf = (float)x + dx, yf = (float)y + dy;
         const float *ib = img + (long)b * is.b;
         float *ob = out + (long)b * C * HW + p;
         if (!bilinear) {   // nearest ignores kernel_size (:64-69)
-            const int xN = clampi(clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1), 0, Wi - 1);
-            const int yN = clampi(clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1), 0, Hi - 1);
+            int xN, xR, yN, yB;
+            float a = 0.0f, be = 0.0f;
+            warp_fwd_corners(x, y, dx, dy, H, W, Hi, Wi, 0, xN, xR, yN, yB, a, be);
             for (int c = 0; c < C; ++c) ob[(long)c * HW] = ib[(long)c * is.c + yN * is.h + xN * is.w];
             continue;
         }
+        const float xf = (float)x + dx, yf = (float)y + dy;
         const float fx0 = floorf(xf), fy0 = floorf(yf);
-        const double a = (double)(xf - fx0), be = (double)(yf - fy0);
+        // the flow's clamp only (the shifted corners are clamped to the image below); warp_pos here changes the kernel's code
         const int xL = clampi(f2i_sat(fx0), 0, W - 1), xR = clampi(f2i_sat(fx0 + 1.0f), 0, W - 1);
         const int yT = clampi(f2i_sat(fy0), 0, H - 1), yB = clampi(f2i_sat(fy0 + 1.0f), 0, H - 1);
-        const double w00 = (1. - a) * (1. - be), w01 = a * (1. - be), w10 = (1. - a) * be, w11 = a * be;
+        const BilinearW w = bilinear_weights(xf - fx0, yf - fy0);
         for (int c = 0; c < C; ++c) {
             const float *ic = ib + (long)c * is.c;
             float val = 0.0f;
@@ -255,10 +239,10 @@ __global__ __launch_bounds__(256) void resample_fwd_ks_kernel(const float *__res
                 for (int fx = 0; fx < ks; ++fx) {
                     const long yt = clampi(yT + fy, 0, Hi - 1) * is.h, yb = clampi(yB + fy, 0, Hi - 1) * is.h;
                     const long xl = clampi(xL + fx, 0, Wi - 1) * is.w, xr = clampi(xR + fx, 0, Wi - 1) * is.w;
-                    val = val + (float)(w00 * (double)ic[yt + xl]);
-                    val = val + (float)(w01 * (double)ic[yt + xr]);
-                    val = val + (float)(w10 * (double)ic[yb + xl]);
-                    val = val + (float)(w11 * (double)ic[yb + xr]);
+                    val = val + (float)(w.w00 * (double)ic[yt + xl]);   // one running sum over the window: not bilinear_sample's, which starts at 0
+                    val = val + (float)(w.w01 * (double)ic[yt + xr]);
+                    val = val + (float)(w.w10 * (double)ic[yb + xl]);
+                    val = val + (float)(w.w11 * (double)ic[yb + xr]);
                 }
             ob[(long)c * HW] = val;
         }
@@ -281,11 +265,10 @@ __global__ __launch_bounds__(256) void resample_bwd_ks_kernel(const float *__res
         const int b = (int)(row / H);
         const long p = (long)y * W + x;
         const float dx = flow[(long)b * 2 * HW + p], dy = flow[(long)b * 2 * HW + HW + p];
-        const float xf = (float)x + dx, yf = (float)y + dy;
-        const float fx0 = floorf(xf), fy0 = floorf(yf);
-        const int ixL = f2i_sat(fx0), ixR = f2i_sat(fx0 + 1.0f), iyT = f2i_sat(fy0), iyB = f2i_sat(fy0 + 1.0f);
+        int ixL, ixR, iyT, iyB;
+        float alpha, beta, fa, fb;
+        warp_bwd_pos(x, y, dx, dy, ixL, ixR, iyT, iyB, alpha, beta, fa, fb);
         // grad_img (:105-123): truncation weights, corners clamped with the image dims, float math
-        const float alpha = xf - (float)f2i_sat(xf), beta = yf - (float)f2i_sat(yf);
         const int sxL = clampi(ixL, 0, Wi - 1), sxR = clampi(ixR, 0, Wi - 1);
         const int syT = clampi(iyT, 0, Hi - 1), syB = clampi(iyB, 0, Hi - 1);
         const float s00 = (1 - alpha) * (1 - beta), s01 = alpha * (1 - beta), s10 = (1 - alpha) * beta, s11 = alpha * beta;
@@ -316,7 +299,7 @@ __global__ __launch_bounds__(256) void resample_bwd_ks_kernel(const float *__res
         }
         // grad_flow (:163-192): corners clamped with the flow dims, loops i (x offset), j (y offset), channel
         const int gxL = clampi(ixL, 0, W - 1), gxR = clampi(ixR, 0, W - 1), gyT = clampi(iyT, 0, H - 1), gyB = clampi(iyB, 0, H - 1);
-        const float gam_y = 1 - (xf - fx0), gam_x = 1 - (yf - fy0);
+        const float gam_y = 1 - fa, gam_x = 1 - fb;   // (:169, :182)
         float out_dx = 0.0f, out_dy = 0.0f;
         for (int i = 0; i <= span; ++i)
             for (int j = 0; j <= span; ++j)
@@ -326,14 +309,7 @@ __global__ __launch_bounds__(256) void resample_bwd_ks_kernel(const float *__res
                     const long yb = clampi(gyB + j, 0, Hi - 1) * is.h, yt = clampi(gyT + j, 0, Hi - 1) * is.h;
                     const long xl = clampi(gxL + i, 0, Wi - 1) * is.w, xr = clampi(gxR + i, 0, Wi - 1) * is.w;
                     const float iTL = I[yt + xl], iTR = I[yt + xr], iBL = I[yb + xl], iBR = I[yb + xr];
-                    out_dy = out_dy + (gam_y * go) * iBL;
-                    out_dy = out_dy - (gam_y * go) * iTL;
-                    out_dy = out_dy + ((1 - gam_y) * go) * iBR;
-                    out_dy = out_dy - ((1 - gam_y) * go) * iTR;
-                    out_dx = out_dx + (gam_x * go) * iTR;
-                    out_dx = out_dx - (gam_x * go) * iTL;
-                    out_dx = out_dx + ((1 - gam_x) * go) * iBR;
-                    out_dx = out_dx - ((1 - gam_x) * go) * iBL;
+                    flow_grad_terms(out_dx, out_dy, gam_x, gam_y, go, iTL, iTR, iBL, iBR);
                 }
         gflow[(long)b * 2 * HW + p] = out_dx;
         gflow[(long)b * 2 * HW + HW + p] = out_dy;
@@ -414,19 +390,8 @@ __global__ __launch_bounds__(1024, 8) void resample_fwd_tiled(const float *__res
         if (!((x < W) && (y < H))) continue;
         const long p = (long)y * W + x;
         const float dx = flow[(long)b * 2 * HW + p], dy = flow[(long)b * 2 * HW + HW + p];
-        const float xf = (float)x + dx, yf = (float)y + dy;
         int xL, xR, yT, yB;
-        if (bilinear) {
-            const float fx = floorf(xf), fy = floorf(yf);
-            alpha[k] = xf - fx; beta[k] = yf - fy;                     // (:45-46)
-            xL = clampi(clampi(f2i_sat(fx), 0, W - 1), 0, Wi - 1);     // clamped with the OUTPUT dims (:49-52)
-            xR = clampi(clampi(f2i_sat(fx + 1.0f), 0, W - 1), 0, Wi - 1);
-            yT = clampi(clampi(f2i_sat(fy), 0, H - 1), 0, Hi - 1);
-            yB = clampi(clampi(f2i_sat(fy + 1.0f), 0, H - 1), 0, Hi - 1);
-        } else {
-            xL = xR = clampi(clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1), 0, Wi - 1);   // (:66-67)
-            yT = yB = clampi(clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1), 0, Hi - 1);
-        }
+        warp_fwd_corners(x, y, dx, dy, H, W, Hi, Wi, bilinear, xL, xR, yT, yB, alpha[k], beta[k]);
         const int lxL = xL - wx0, lxR = xR - wx0, lyT = yT - wy0, lyB = yB - wy0;
         const bool in = (lxL >= 0) && (lxR < WW) && (lyT >= 0) && (lyB < WH);
         base[k] = in ? lyT * WW + lxL : yT * (int)is.h + xL * (int)is.w;
@@ -478,17 +443,7 @@ __global__ __launch_bounds__(1024, 8) void resample_fwd_tiled(const float *__res
                 const int ox = (fl & DX) ? (int)is.w : 0, oy = (fl & DY) ? (int)is.h : 0;
                 i00 = I[o]; i01 = I[o + ox]; i10 = I[o + oy]; i11 = I[o + oy + ox];
             }
-            float val;
-            if (bilinear) {
-                const double a = (double)alpha[k], be = (double)beta[k];   // "1." literals -> double (:56-59)
-                val = 0.0f;
-                val = val + (float)(((1. - a) * (1. - be)) * (double)i00);
-                val = val + (float)((a * (1. - be)) * (double)i01);
-                val = val + (float)(((1. - a) * be) * (double)i10);
-                val = val + (float)((a * be) * (double)i11);
-            } else {
-                val = i00;
-            }
+            const float val = bilinear ? bilinear_sample(alpha[k], beta[k], i00, i01, i10, i11) : i00;
             if (!FUSE) store_out(out + ((long)b * C + c) * HW + (y * W + x), val);
             else {
                 const int pix = y * W + x;
@@ -579,20 +534,9 @@ __global__ __launch_bounds__(TH * 16, (2 * TH * 16 + 255) / 256) void resample_f
     int base[4], flags[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float xf = (float)(x0 + k) + vdx[k], yf = (float)y + vdy[k];
         int xL, xR, yT, yB;
         alpha[k] = beta[k] = 0.0f;
-        if (bilinear) {
-            const float fx = floorf(xf), fy = floorf(yf);
-            alpha[k] = xf - fx; beta[k] = yf - fy;                     // (:45-46)
-            xL = clampi(clampi(f2i_sat(fx), 0, W - 1), 0, Wi - 1);     // clamped with the OUTPUT dims (:49-52)
-            xR = clampi(clampi(f2i_sat(fx + 1.0f), 0, W - 1), 0, Wi - 1);
-            yT = clampi(clampi(f2i_sat(fy), 0, H - 1), 0, Hi - 1);
-            yB = clampi(clampi(f2i_sat(fy + 1.0f), 0, H - 1), 0, Hi - 1);
-        } else {
-            xL = xR = clampi(clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1), 0, Wi - 1);   // (:66-67)
-            yT = yB = clampi(clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1), 0, Hi - 1);
-        }
+        warp_fwd_corners(x0 + k, y, vdx[k], vdy[k], H, W, Hi, Wi, bilinear, xL, xR, yT, yB, alpha[k], beta[k]);
         const int lxL = xL - wx0, lxR = xR - wx0, lyT = yT - wy0, lyB = yB - wy0;
         const bool in = (lxL >= 0) && (lxR < WW) && (lyT >= 0) && (lyB < WH);
         base[k] = in ? lyT * WW + lxL : yT * (int)is.h + xL * (int)is.w;
@@ -617,17 +561,7 @@ __global__ __launch_bounds__(TH * 16, (2 * TH * 16 + 255) / 256) void resample_f
                 const int ox = (fl & DX) ? (int)is.w : 0, oy = (fl & DY) ? (int)is.h : 0;
                 i00 = I[o]; i01 = I[o + ox]; i10 = I[o + oy]; i11 = I[o + oy + ox];
             }
-            float val;
-            if (bilinear) {
-                const double a = (double)alpha[k], be = (double)beta[k];   // "1." literals -> double (:56-59)
-                val = 0.0f;
-                val = val + (float)(((1. - a) * (1. - be)) * (double)i00);
-                val = val + (float)((a * (1. - be)) * (double)i01);
-                val = val + (float)(((1. - a) * be) * (double)i10);
-                val = val + (float)((a * be) * (double)i11);
-            } else {
-                val = i00;
-            }
+            const float val = bilinear ? bilinear_sample(alpha[k], beta[k], i00, i01, i10, i11) : i00;
             res[k] = val;
         }
         if (live) store_out(reinterpret_cast<f4 *>(out + ((long)b * C + c) * HW + p0), res);
@@ -690,24 +624,12 @@ __device__ __forceinline__ void fwd_tile_all(float *__restrict__ win, const floa
         const int idx = tid + NT * k;
         const int x = X0 + idx % TW, y = Y0 + idx / TW;
         if (!((x < W) && (y < ylim))) continue;
-        const float xf = (float)x + fdx[k], yf = (float)y + fdy[k];
         int xL, xR, yT, yB;
         float alpha = 0.0f, beta = 0.0f;
-        if (bilinear) {
-            const float fx = floorf(xf), fy = floorf(yf);
-            alpha = xf - fx; beta = yf - fy;                           // (:45-46)
-            xL = clampi(clampi(f2i_sat(fx), 0, W - 1), 0, Wi - 1);     // clamped with the OUTPUT dims (:49-52)
-            xR = clampi(clampi(f2i_sat(fx + 1.0f), 0, W - 1), 0, Wi - 1);
-            yT = clampi(clampi(f2i_sat(fy), 0, H - 1), 0, Hi - 1);
-            yB = clampi(clampi(f2i_sat(fy + 1.0f), 0, H - 1), 0, Hi - 1);
-        } else {
-            xL = xR = clampi(clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1), 0, Wi - 1);   // (:66-67)
-            yT = yB = clampi(clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1), 0, Hi - 1);
-        }
+        warp_fwd_corners(x, y, fdx[k], fdy[k], H, W, Hi, Wi, bilinear, xL, xR, yT, yB, alpha, beta);
         const int lxL = xL - wx0, lxR = xR - wx0, lyT = yT - wy0, lyB = yB - wy0;
         const bool in = (lxL >= 0) && (lxR < WW) && (lyT >= 0) && (lyB < WH);
-        const double a = (double)alpha, be = (double)beta;             // "1." literals -> double (:56-59)
-        const double w00 = (1. - a) * (1. - be), w01 = a * (1. - be), w10 = (1. - a) * be, w11 = a * be;
+        const BilinearW w = bilinear_weights(alpha, beta);
         const int o = in ? lyT * WW + lxL : yT * (int)is.h + xL * (int)is.w;
         const int ox = (xR != xL) ? (in ? 1 : (int)is.w) : 0, oy = (yB != yT) ? (in ? WW : (int)is.h) : 0;
 #pragma unroll
@@ -720,17 +642,7 @@ __device__ __forceinline__ void fwd_tile_all(float *__restrict__ win, const floa
                 const float *I = img + (long)b * is.b + (long)c * is.c;
                 i00 = I[o]; i01 = I[o + ox]; i10 = I[o + oy]; i11 = I[o + oy + ox];
             }
-            float val;
-            if (bilinear) {
-                val = 0.0f;
-                val = val + (float)(w00 * (double)i00);
-                val = val + (float)(w01 * (double)i01);
-                val = val + (float)(w10 * (double)i10);
-                val = val + (float)(w11 * (double)i11);
-            } else {
-                val = i00;
-            }
-            store_out(out + ((long)b * NC + c) * HW + (y * W + x), val);
+            store_out(out + ((long)b * NC + c) * HW + (y * W + x), bilinear ? bilinear_sample(w, i00, i01, i10, i11) : i00);
         }
     }
     if (ts) ts[3] = wall_clock64();
@@ -890,12 +802,10 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
         if (!((x < W) && (y < H))) continue;
         int fl = LIVE;
         const float dx = fdx[k], dy = fdy[k];
-        const float xf = (float)x + dx, yf = (float)y + dy;
-        const float fx = floorf(xf), fy = floorf(yf);
-        const int ixL = f2i_sat(fx), ixR = f2i_sat(fx + 1.0f), iyT = f2i_sat(fy), iyB = f2i_sat(fy + 1.0f);
-        alpha[k] = xf - (float)f2i_sat(xf); beta[k] = yf - (float)f2i_sat(yf);   // truncation (:105-106)
-        gam_y[k] = 1 - (xf - fx);   // c == 1 branch (:169)
-        gam_x[k] = 1 - (yf - fy);   // c == 0 branch (:182)
+        int ixL, ixR, iyT, iyB;
+        float fa, fb;
+        warp_bwd_pos(x, y, dx, dy, ixL, ixR, iyT, iyB, alpha[k], beta[k], fa, fb);
+        gam_y[k] = 1 - fa; gam_x[k] = 1 - fb;   // (:169, :182)
         {   // scatter corners: clamped with the INPUT1 dims (:108-114)
             const int xL = clampi(ixL, 0, Wi - 1), xR = clampi(ixR, 0, Wi - 1);
             const int yT = clampi(iyT, 0, Hi - 1), yB = clampi(iyB, 0, Hi - 1);
@@ -989,6 +899,7 @@ __global__ __launch_bounds__(NT, WPE) void resample_bwd_tiled(const float *__res
                 const int ox = (fl & G_DX) ? (int)is.w : 0, oy = (fl & G_DY) ? (int)is.h : 0;
                 iTL = I[gb]; iTR = I[gb + ox]; iBL = I[gb + oy]; iBR = I[gb + oy + ox];
             }
+            // written out: flow_grad_terms here changes the code of the wider profiling instantiations
             out_dy[k] = out_dy[k] + (gam_y[k] * go) * iBL;       // (:172-177)
             out_dy[k] = out_dy[k] - (gam_y[k] * go) * iTL;
             out_dy[k] = out_dy[k] + ((1 - gam_y[k]) * go) * iBR;
@@ -1225,6 +1136,7 @@ __global__ __launch_bounds__(NT, 8) void resample_bwd_c3x(const C3xArgs p)
         gbase[k] = flags[k] = 0;
         if (!((x < W) && (y < H))) continue;
         int fl = LIVE;
+        // written out: warp_bwd_pos forms the scatter's alpha / beta ahead of the `continue` below, which reorders this kernel's code
         const float xf = (float)x + fdx[k], yf = (float)y + fdy[k];
         const float fx = floorf(xf), fy = floorf(yf);
         const int ixL = f2i_sat(fx), ixR = f2i_sat(fx + 1.0f), iyT = f2i_sat(fy), iyB = f2i_sat(fy + 1.0f);
@@ -1338,7 +1250,7 @@ __global__ __launch_bounds__(NT, 8) void resample_bwd_c3x(const C3xArgs p)
             if constexpr (FUSED == 2) {
                 // the forward's sample (resample2d_kernel.cu:56-59 / :66-69) from the same four corners, then ChannelNorm's gradient of
                 // the difference (channelnorm_kernel.cu:93) with the sign of d(diff)/d(warped)
-                float val;
+                float val;   // warp_value<true>, written out: the helper (or bilinear_sample alone) reorders this kernel's code
                 if (p.bilinear) {
                     const double a = (double)alv[k], be = (double)btv[k];
                     val = 0.0f;
@@ -1351,14 +1263,7 @@ __global__ __launch_bounds__(NT, 8) void resample_bwd_c3x(const C3xArgs p)
                 }
                 g = 0.0f - chnorm_grad(gnv[k], g - val, nrv[k]);
             }
-            out_dy = out_dy + (gam_y[k] * g) * iBL;       // (:172-177)
-            out_dy = out_dy - (gam_y[k] * g) * iTL;
-            out_dy = out_dy + ((1 - gam_y[k]) * g) * iBR;
-            out_dy = out_dy - ((1 - gam_y[k]) * g) * iTR;
-            out_dx = out_dx + (gam_x[k] * g) * iTR;       // (:185-190)
-            out_dx = out_dx - (gam_x[k] * g) * iTL;
-            out_dx = out_dx + ((1 - gam_x[k]) * g) * iBR;
-            out_dx = out_dx - ((1 - gam_x[k]) * g) * iBL;
+            flow_grad_terms(out_dx, out_dy, gam_x[k], gam_y[k], g, iTL, iTR, iBL, iBR);
         }
         const int idx = tid + NT * k;
         const int x = X0 + idx % TW, y = Y0 + idx / TW;
@@ -1397,6 +1302,7 @@ __global__ __launch_bounds__(256) void warp_diff_norm_cat_bwd_kernel(const float
         const long row = g / W;
         const int y = (int)(row % H), b = (int)(row / H);
         const long pix = (long)y * W + x;
+        // position, sample and flow gradient written out: each shared helper (resample2d_common.h) changes this kernel's code
         const float xf = (float)x + flow[(long)b * 2 * HW + pix], yf = (float)y + flow[(long)b * 2 * HW + HW + pix];
         const float fx = floorf(xf), fy = floorf(yf);
         const int ixL = f2i_sat(fx), ixR = f2i_sat(fx + 1.0f), iyT = f2i_sat(fy), iyB = f2i_sat(fy + 1.0f);
@@ -1524,6 +1430,7 @@ __device__ void det_fallback(const DetSrc &d, const float *__restrict__ flow, co
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
             const long p = (long)y * W + x;
+            // written out: warp_bwd_pos converts in another order, which changes this kernel's branches
             const float xf = (float)x + flow[(long)b * 2 * HW + p], yf = (float)y + flow[(long)b * 2 * HW + HW + p];
             const float alpha = xf - (float)f2i_sat(xf), beta = yf - (float)f2i_sat(yf);
             const float fx = floorf(xf), fy = floorf(yf);
@@ -1579,29 +1486,25 @@ __global__ __launch_bounds__(256) void warp_diff_norm_cat_kernel(const float *__
         const long pix = (long)y * W + x;
         const float dx = flow[(long)b * 2 * HW + pix], dy = flow[(long)b * 2 * HW + HW + pix];
         const float xf = (float)x + dx, yf = (float)y + dy;
-        int xL, xR, yT, yB;
-        double a = 0., be = 0.;
+        int xL, xR, yT, yB;   // one clamp (the image has the flow's size), written out: warp_pos / warp_fwd_corners change this kernel's code
+        float alpha = 0.0f, beta = 0.0f;
         if (bilinear) {
             const float fx = floorf(xf), fy = floorf(yf);
-            a = (double)(xf - fx); be = (double)(yf - fy);
+            alpha = xf - fx; beta = yf - fy;
             xL = clampi(f2i_sat(fx), 0, W - 1); xR = clampi(f2i_sat(fx + 1.0f), 0, W - 1);
             yT = clampi(f2i_sat(fy), 0, H - 1); yB = clampi(f2i_sat(fy + 1.0f), 0, H - 1);
         } else {
             xL = xR = clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1);
             yT = yB = clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1);
         }
+        const BilinearW w = bilinear_weights(alpha, beta);
         float *ob = out + (long)b * (3 * C + 3) * HW + pix;
         float ssq = 0.0f;
         for (int c = 0; c < C; ++c) {
             const float *I = pair + ((long)b * 2 * C + C + c) * HW;
             float val;
-            if (bilinear) {
-                val = 0.0f;
-                val = val + (float)(((1. - a) * (1. - be)) * (double)I[(long)yT * W + xL]);
-                val = val + (float)((a * (1. - be)) * (double)I[(long)yT * W + xR]);
-                val = val + (float)(((1. - a) * be) * (double)I[(long)yB * W + xL]);
-                val = val + (float)((a * be) * (double)I[(long)yB * W + xR]);
-            } else val = I[(long)yT * W + xL];
+            if (bilinear) val = bilinear_sample(w, I[(long)yT * W + xL], I[(long)yT * W + xR], I[(long)yB * W + xL], I[(long)yB * W + xR]);
+            else val = I[(long)yT * W + xL];
             const float v0 = pair[((long)b * 2 * C + c) * HW + pix];
             if (!norm_only) {
                 ob[(long)c * HW] = v0;
@@ -1629,114 +1532,158 @@ static inline int tile_height(int B, int H, int tiles_x)
     return c48 < c32 ? 48 : 32;
 }
 
-static inline unsigned stream_grid(long nthreads)
-{
-    long blocks = (nthreads + 255) / 256;
-    const long cap = 256L * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 } // namespace fn2
 
-// argument block of resample_bwd_c3x for 32 x 64 tiles (the fields of the fused form are set by its caller)
-static fn2::C3xArgs c3x_args(const float *img, fn2::ImgStrides is, const float *flow, float *gimg, long gimg_bs, float *gflow,
-                             int B, int Hi, int Wi, int H, int W, int tiles_x, int abl)
+// ---------------------------------------------------------------- host side: checks, strides, launches
+using namespace fn2;
+
+// The checks come in the same order in every entry point: dims (with kernel_size / div_flow) -> FN2_EINVAL, empty -> FN2_OK,
+// null -> FN2_EINVAL, (det) workspace -> FN2_EINVAL, alignment -> FN2_EALIGN.
+static bool resample_dims_bad(int B, int C, int Hi, int Wi, int H, int W, int kernel_size)
 {
-    fn2::C3xArgs a;
+    return B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0 || kernel_size < 1;
+}
+static bool pair_dims_bad(int B, int C, int H, int W, float div_flow = 1.0f)
+{
+    return B < 0 || C < 1 || H < 1 || W < 1 || !(div_flow == div_flow) || div_flow == 0.0f;
+}
+template <class... P> static bool any_null(P... p) { return (... || (p == nullptr)); }
+template <class... P> static bool all_aligned(size_t bytes, P... p) { return (... && aligned(p, bytes)); }
+
+// the caller's strides, or those of a dense B x C x Hi x Wi image
+static ImgStrides dense_or(const int64_t *st, int C, int Hi, int Wi)
+{
+    if (st) return ImgStrides{st[0], st[1], st[2], st[3]};
+    return ImgStrides{(long)C * Hi * Wi, (long)Hi * Wi, Wi, 1};
+}
+// the second image of a dense B x 2C x H x W pair (the one that is warped) and its strides
+static const float *pair_second(const float *pair, int C, int H, int W, ImgStrides &is)
+{
+    const long HW = (long)H * W;
+    is = ImgStrides{2L * C * HW, HW, W, 1};
+    return pair + (long)C * HW;
+}
+// shapes the LDS-window kernels take: image rows contiguous and 16 B aligned, same size as the flow, large enough to tile
+static bool tiled_shape_ok(const ImgStrides &is, const float *img, int Hi, int Wi, int H, int W)
+{
+    return (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && aligned(img, 16) && (Hi == H) && (Wi == W) &&
+           (W % 4 == 0) && (H >= 16) && (W >= 32);
+}
+static dim3 tile_grid(int B, int tiles_x, int tiles_y) { return dim3((unsigned)((long)B * tiles_x * tiles_y)); }
+
+// resample_fwd_tiled<TH, 64, 16, FUSE> on a tiled shape (image of the flow's size), TH = 32 or 48: `th`, or tile_height's choice
+template <int FUSE>
+static void launch_fwd_tiled(const float *img, const ImgStrides &is, const float *flow, float *out, int B, int C, int H, int W, int bilinear,
+                             const float *pair, float div_flow, hipStream_t s, int th = 0)
+{
+    const int tiles_x = (W + 63) / 64;
+    if (!th) th = tile_height(B, H, tiles_x);
+    const int tiles_y = (H + th - 1) / th;
+    if (th == 48)
+        hipLaunchKernelGGL((resample_fwd_tiled<48, 64, 16, FUSE>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow, out, C, H,
+                           W, H, W, tiles_x, tiles_y, bilinear, pair, div_flow);
+    else
+        hipLaunchKernelGGL((resample_fwd_tiled<32, 64, 16, FUSE>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow, out, C, H,
+                           W, H, W, tiles_x, tiles_y, bilinear, pair, div_flow);
+}
+
+// argument block of resample_bwd_c3x for 32 x 64 tiles (the fields of the fused form are set by its caller)
+static C3xArgs c3x_args(const float *img, ImgStrides is, const float *flow, float *gimg, long gimg_bs, float *gflow, int B, int Hi, int Wi,
+                        int H, int W, int abl)
+{
+    C3xArgs a;
     a.img = img; a.is = is; a.flow = flow; a.gout = nullptr; a.gcat = a.pair = a.outcat = nullptr; a.gpair0 = nullptr;
     a.gimg = gimg; a.gimg_bs = gimg_bs; a.gflow = gflow;
-    a.B = B; a.Hi = Hi; a.Wi = Wi; a.H = H; a.W = W; a.tiles_x = tiles_x; a.tiles_y = (H + 31) / 32; a.abl = abl;
+    a.B = B; a.Hi = Hi; a.Wi = Wi; a.H = H; a.W = W; a.tiles_x = (W + 63) / 64; a.tiles_y = (H + 31) / 32; a.abl = abl;
     a.inv_div_flow = 0.0f; a.bilinear = 1;
 #ifdef FN2_DEBUG_BUILD
-    a.dbg = static_cast<unsigned long long *>(fn2::corr_f16x2_get_debug_buffer());
+    a.dbg = static_cast<unsigned long long *>(corr_f16x2_get_debug_buffer());
 #else
     a.dbg = nullptr;
 #endif
     return a;
 }
-static unsigned c3x_grid(const fn2::C3xArgs &a) { return (unsigned)((long)a.B * a.tiles_x * a.tiles_y); }
+template <int FUSED, bool SCATTER> static void launch_c3x(const C3xArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, FUSED, SCATTER>), tile_grid(a.B, a.tiles_x, a.tiles_y), dim3(1024), 0, s, a);
+}
 
-// `bilinear`: bit 0 = bilinear (else nearest); bits 8.. = profiling switches that only fn2_debug_resample2d_* set
-// (bit 8: untiled kernels, bits 9-11: backward ablations, bits 12-13: tile height)
+// grad_pair[:, C:] = grad_cat[:, C:2C]: the second image's gradient starts as its slice of the concat gradient (one strided copy), then
+// the scatter adds
+static hipError_t seed_second_grad(float *grad_pair, const float *grad_cat, int B, int C, long HW, hipStream_t s)
+{
+    return hipMemcpy2DAsync(grad_pair + (long)C * HW, 2 * C * HW * sizeof(float), grad_cat + (long)C * HW, (3 * C + 3) * HW * sizeof(float),
+                            C * HW * sizeof(float), B, hipMemcpyDeviceToDevice, s);
+}
+
+// `bilinear` of the two impl functions: bit 0 = bilinear (else nearest; both reference backward kernels ignore it); the
+// bits from 8 up are profiling switches that only fn2_debug_resample2d_* set (0 from the public entry points and the bindings).  The
+// values are the ones the scripts pass (scripts/resample_micro.py, resample_r5_micro.py, resample_timeline.py).
+enum : int {
+    RS_BILINEAR = 1,
+    RS_UNTILED = 0x100,    // bit 8: the untiled kernels
+    RS_ABL_SHIFT = 9,      // bits 9-11: the backward kernels' ablations (`abl` bits 0-2: no flush, no scatter, no gather)
+    RS_TILE_SHIFT = 12,    // bits 12-13: tile height, 0 = automatic (1 = 48, 2 = 32, 3 = 96 with every channel resident forward, 64 backward)
+    RS_FORM_SHIFT = 14,    // bits 14-15, forward: 4 adjacent pixels per thread (1 = 48 x 64 tiles, 2 = 64 x 64); backward: accumulation window
+                           // (1 = fp64 cells 48 x 64 +- 12, 2 = fp64 cells 32 x 64 +- 16, 3 = fp64 cells 48 x 64 +- 16, one workgroup per CU)
+    RS_STAMPS = 0x10000,   // bit 16: wall-clock stamps into the debug buffer (`abl` bit 3)
+};
+static int rs_tile(int f) { return (f >> RS_TILE_SHIFT) & 3; }
+static int rs_form(int f) { return (f >> RS_FORM_SHIFT) & 3; }
+static int rs_variant(int f) { return (f >> RS_TILE_SHIFT) & 15; }   // tile and form bits together: the backward's selector
+static int rs_abl(int f) { return ((f >> RS_ABL_SHIFT) & 7) | ((f & RS_STAMPS) ? 8 : 0); }
+
 static int resample2d_forward_impl(const float *img, const int64_t *img_strides, const float *flow, float *out,
                                    int B, int C, int Hi, int Wi, int H, int W,
                                    int kernel_size, int bilinear, void *stream)
 {
-    using namespace fn2;
-    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0) return FN2_EINVAL;
-    if (kernel_size < 1) return FN2_EINVAL;
+    if (resample_dims_bad(B, C, Hi, Wi, H, W, kernel_size)) return FN2_EINVAL;
     if ((long)B * C * H * W == 0) return FN2_OK;
-    if (!img || !flow || !out) return FN2_EINVAL;
-    if (!aligned(img, 4) || !aligned(flow, 4) || !aligned(out, 4)) return FN2_EALIGN;
-    ImgStrides is;
-    if (img_strides) { is.b = img_strides[0]; is.c = img_strides[1]; is.h = img_strides[2]; is.w = img_strides[3]; }
-    else { is.b = (long)C * Hi * Wi; is.c = (long)Hi * Wi; is.h = Wi; is.w = 1; }
+    if (any_null(img, flow, out)) return FN2_EINVAL;
+    if (!all_aligned(4, img, flow, out)) return FN2_EALIGN;
+    const ImgStrides is = dense_or(img_strides, C, Hi, Wi);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long npix = (long)B * H * W;
+    const int bil = bilinear & RS_BILINEAR;
     if (kernel_size != 1) {
         hipLaunchKernelGGL(resample_fwd_ks_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, out, C, Hi, Wi, H, W,
-                           npix, kernel_size, (bilinear & 1) ? 1 : 0);
-        return launch_status();
-    }
-    // tiled path: image rows contiguous and 16 B aligned, same size as the flow, large enough to tile
-    const bool tiled_ok = (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && aligned(img, 16) &&
-                          (Hi == H) && (Wi == W) && (W % 4 == 0) && (H >= 16) && (W >= 32) && !(bilinear & 0x100);
-    if (tiled_ok) {
-        constexpr int TW = 64;
-        const int tiles_x = (W + TW - 1) / TW;
-#define FN2_RF(TH)                                                                                                     \
-    do {                                                                                                               \
-        const int tiles_y = (H + TH - 1) / TH;                                                                         \
-        hipLaunchKernelGGL((resample_fwd_tiled<TH, TW, 16>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), \
-                           0, s, img, is, flow, out, C, Hi, Wi, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0);       \
-    } while (0)
-        if (((bilinear >> 14) & 3) == 1 && aligned(flow, 16) && aligned(out, 16)) {   // profiling: 4 adjacent pixels per thread, 48 x 64 tiles
+                           npix, kernel_size, bil);
+    } else if (tiled_shape_ok(is, img, Hi, Wi, H, W) && !(bilinear & RS_UNTILED)) {
+        const int tiles_x = (W + 63) / 64, px4 = all_aligned(16, flow, out) ? rs_form(bilinear) : 0;
+        if (px4 == 1) {          // profiling: 4 adjacent pixels per thread, 48 x 64 tiles
             const int tiles_y = (H + 47) / 48;
-            hipLaunchKernelGGL((resample_fwd_tiled4<48, 16>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(768), 0, s,
-                               img, is, flow, out, C, Hi, Wi, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0);
-            return launch_status();
-        }
-        if (((bilinear >> 14) & 3) == 2 && aligned(flow, 16) && aligned(out, 16)) {   // ... 64 x 64 tiles, 1024 threads
+            hipLaunchKernelGGL((resample_fwd_tiled4<48, 16>), tile_grid(B, tiles_x, tiles_y), dim3(768), 0, s, img, is, flow, out, C, Hi, Wi,
+                               H, W, tiles_x, tiles_y, bil);
+        } else if (px4 == 2) {   // ... 64 x 64 tiles, 1024 threads
             const int tiles_y = (H + 63) / 64;
-            hipLaunchKernelGGL((resample_fwd_tiled4<64, 16>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), 0, s,
-                               img, is, flow, out, C, Hi, Wi, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0);
-            return launch_status();
-        }
-        if (((bilinear >> 12) & 3) == 3 && C == 3) {   // profiling: every channel window resident, 96 x 64 tiles, one workgroup per CU
+            hipLaunchKernelGGL((resample_fwd_tiled4<64, 16>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow, out, C, Hi, Wi,
+                               H, W, tiles_x, tiles_y, bil);
+        } else if (rs_tile(bilinear) == 3 && C == 3) {   // profiling: every channel window resident, 96 x 64 tiles, one workgroup per CU
             const int tiles_y = (H + 95) / 96;
-            hipLaunchKernelGGL((resample_fwd_tiled_all<96, TW, 16, 3>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), 0, s,
-                               img, is, flow, out, Hi, Wi, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0);
-            return launch_status();
-        }
-        if (((bilinear >> 12) & 15) == 0 && C == 3) {
+            hipLaunchKernelGGL((resample_fwd_tiled_all<96, 64, 16, 3>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow, out,
+                               Hi, Wi, H, W, tiles_x, tiles_y, bil);
+        } else if (rs_variant(bilinear) == 0 && C == 3) {
             // C == 3 (FlowNet2's only use): the three channel windows resident at once in 32 x 64 tiles (73.7 KB: two workgroups per
             // CU), one barrier in the whole kernel, corner offsets and weights formed once per pixel -- 8 x 3 x 384 x 512: 19.3 us
             // against 20.9 for the per-channel kernel (smooth flow 18.1 / 19.1), same bits
             const int tiles_y = (H + 31) / 32;
             unsigned long long *dbgbuf = nullptr;
 #ifdef FN2_DEBUG_BUILD
-            if (bilinear & 0x10000) dbgbuf = static_cast<unsigned long long *>(corr_f16x2_get_debug_buffer());   // profiling: timeline stamps
+            if (bilinear & RS_STAMPS) dbgbuf = static_cast<unsigned long long *>(corr_f16x2_get_debug_buffer());   // profiling: timeline stamps
 #endif
             // (512 persistent workgroups taking one tile and then half of one of the remaining 256 -- one balanced round instead of one
             // and a half -- measured slower: 18.6 us against 17.0, the half tile costs 4.8 us of fixed latencies)
-            hipLaunchKernelGGL((resample_fwd_tiled_all<32, TW, 16, 3, 8>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), 0, s,
-                               img, is, flow, out, Hi, Wi, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0, dbgbuf);
-            return launch_status();
+            hipLaunchKernelGGL((resample_fwd_tiled_all<32, 64, 16, 3, 8>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow,
+                               out, Hi, Wi, H, W, tiles_x, tiles_y, bil, dbgbuf);
+        } else {
+            const int th = rs_tile(bilinear) ? (rs_tile(bilinear) == 1 ? 48 : 32) : 0;   // profiling: a forced tile height
+            launch_fwd_tiled<0>(img, is, flow, out, B, C, H, W, bil, nullptr, 1.0f, s, th);
         }
-        const int th = (bilinear >> 12) & 3 ? ((bilinear >> 12) & 3) == 1 ? 48 : 32 : tile_height(B, H, tiles_x);
-        if (th == 48) FN2_RF(48); else FN2_RF(32);
-#undef FN2_RF
-        return launch_status();
-    }
-    if (W % 4 == 0 && aligned(flow, 16) && aligned(out, 16)) {
+    } else if (W % 4 == 0 && all_aligned(16, flow, out)) {
         const long ng = npix / 4;
-        hipLaunchKernelGGL(resample_fwd_kernel<4>, dim3(stream_grid(ng)), dim3(256), 0, s, img, is, flow, out, C, Hi, Wi,
-                           H, W, ng, (bilinear & 1) ? 1 : 0);
+        hipLaunchKernelGGL(resample_fwd_kernel<4>, dim3(stream_grid(ng)), dim3(256), 0, s, img, is, flow, out, C, Hi, Wi, H, W, ng, bil);
     } else {
-        hipLaunchKernelGGL(resample_fwd_kernel<1>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, out, C, Hi,
-                           Wi, H, W, npix, (bilinear & 1) ? 1 : 0);
+        hipLaunchKernelGGL(resample_fwd_kernel<1>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, out, C, Hi, Wi, H, W, npix, bil);
     }
     return launch_status();
 }
@@ -1763,41 +1710,25 @@ static int resample2d_backward_impl(const float *img, const int64_t *img_strides
                                     int B, int C, int Hi, int Wi, int H, int W,
                                     int kernel_size, int bilinear, void *stream)
 {
-    using namespace fn2;
-    // both reference backward kernels ignore the bilinear flag; bit 8 of it selects the
-    // untiled scatter kernel (profiling / A-B only)
-    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0) return FN2_EINVAL;
-    if (kernel_size < 1) return FN2_EINVAL;
+    if (resample_dims_bad(B, C, Hi, Wi, H, W, kernel_size)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!img || !flow || !grad_out || !grad_img || !grad_flow) return FN2_EINVAL;
-    if (!aligned(img, 4) || !aligned(flow, 4) || !aligned(grad_out, 4) || !aligned(grad_img, 4) || !aligned(grad_flow, 4))
-        return FN2_EALIGN;
-    ImgStrides is;
-    if (img_strides) { is.b = img_strides[0]; is.c = img_strides[1]; is.h = img_strides[2]; is.w = img_strides[3]; }
-    else { is.b = (long)C * Hi * Wi; is.c = (long)Hi * Wi; is.h = Wi; is.w = 1; }
+    if (any_null(img, flow, grad_out, grad_img, grad_flow)) return FN2_EINVAL;
+    if (!all_aligned(4, img, flow, grad_out, grad_img, grad_flow)) return FN2_EALIGN;
+    const ImgStrides is = dense_or(img_strides, C, Hi, Wi);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long npix = (long)B * H * W;
     if (kernel_size != 1) {
         hipLaunchKernelGGL(resample_bwd_ks_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
                            grad_flow, C, Hi, Wi, H, W, npix, kernel_size);
-        return launch_status();
-    }
-    const bool tiled_ok = (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && aligned(img, 16) &&
-                          (Hi == H) && (Wi == W) && (W % 4 == 0) && (H >= 16) && (W >= 32) && !(bilinear & 0x100);
-    if (tiled_ok) {
-        constexpr int TW = 64;
-        const int abl = ((bilinear >> 9) & 7) | ((bilinear & 0x10000) ? 8 : 0);   // bits 9-11, 16 of `bilinear`: profiling switches, 0 from the bindings
-        const int tiles_x = (W + TW - 1) / TW;
+    } else if (tiled_shape_ok(is, img, Hi, Wi, H, W) && !(bilinear & RS_UNTILED)) {
+        const int abl = rs_abl(bilinear), tiles_x = (W + 63) / 64;
 #define FN2_RB(TH, R, WPE, ACC)                                                                                        \
     do {                                                                                                               \
         const int tiles_y = (H + TH - 1) / TH;                                                                         \
-        hipLaunchKernelGGL((resample_bwd_tiled<TH, TW, R, 1024, WPE, ACC>), dim3((unsigned)((long)B * tiles_x * tiles_y)), \
-                           dim3(1024), 0, s, img, is, flow, grad_out, grad_img, grad_flow, C, Hi, Wi, H, W, tiles_x,   \
-                           tiles_y, abl);                                                                              \
+        hipLaunchKernelGGL((resample_bwd_tiled<TH, 64, R, 1024, WPE, ACC>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, \
+                           flow, grad_out, grad_img, grad_flow, C, Hi, Wi, H, W, tiles_x, tiles_y, abl);               \
     } while (0)
-        // bits 12-13: tile height (profiling: 1 = 48, 2 = 32, 3 = 64), 0 = automatic; bits 14-15: accumulation window
-        // (profiling: 1 = fp64 cells 48 x 64 +- 12, 2 = fp64 cells 32 x 64 +- 16, 3 = fp64 cells 48 x 64 +- 16, one workgroup per CU)
-        switch ((bilinear >> 12) & 15) {
+        switch (rs_variant(bilinear)) {   // profiling: tile height and accumulation window (the table above)
         case 1: FN2_RB(48, 16, 8, 0); break;
         case 2: FN2_RB(32, 16, 8, 0); break;
         case 3: FN2_RB(64, 16, 8, 0); break;
@@ -1814,9 +1745,9 @@ static int resample2d_backward_impl(const float *img, const int64_t *img_strides
         // workgroups per CU; selector 8): 54.2 / 38.6 us against 57.2-59.8 / 44.5 for the 48 x 64 fp32 tiles of round 3 (selector 10)
         default:
             if (C == 3) {
-                C3xArgs a = c3x_args(img, is, flow, grad_img, (long)C * Hi * Wi, grad_flow, B, Hi, Wi, H, W, tiles_x, abl);
+                C3xArgs a = c3x_args(img, is, flow, grad_img, (long)C * Hi * Wi, grad_flow, B, Hi, Wi, H, W, abl);
                 a.gout = grad_out;
-                hipLaunchKernelGGL((resample_bwd_c3x<32, TW, 16, 1024, 0, true>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
+                launch_c3x<0, true>(a, s);
             } else FN2_RB(32, 16, 8, 1);
             break;
         }
@@ -1848,138 +1779,93 @@ extern "C" int fn2_debug_resample2d_backward(const float *img, const int64_t *im
 }
 #endif
 
-extern "C" int fn2_warp_diff_norm_cat(const float *pair, const float *flow, float *out, float div_flow,
-                                      int B, int C, int H, int W, int bilinear, void *stream)
+// Row N2 (fn2_warp_diff_norm_cat) and its norm-only form (fn2_warp_diff_norm, models.py:157-161 / :170-174:
+// ||pair[:, :C] - Resample2d(pair[:, C:], flow)||_2 with no concat -- the same kernels storing only the norm plane)
+template <int FUSE>   // 1: the concat; 2: the norm plane only
+static int warp_diff_norm_forward(const float *pair, const float *flow, float *out, float div_flow, int B, int C, int H, int W, int bilinear,
+                                  void *stream)
 {
-    using namespace fn2;
     bilinear = bilinear != 0 ? 1 : 0;
-    if (B < 0 || C < 1 || H < 1 || W < 1 || !(div_flow == div_flow) || div_flow == 0.0f) return FN2_EINVAL;
+    if (pair_dims_bad(B, C, H, W, div_flow)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!pair || !flow || !out) return FN2_EINVAL;
-    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(out, 4)) return FN2_EALIGN;
+    if (any_null(pair, flow, out)) return FN2_EINVAL;
+    if (!all_aligned(4, pair, flow, out)) return FN2_EALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W, npix = (long)B * HW;
-    const bool tiled_ok = (W % 4 == 0) && aligned(pair, 16) && (H >= 16) && (W >= 32) && !(bilinear & 0x100);
-    if (tiled_ok) {
-        ImgStrides is;
-        is.b = 2 * C * HW; is.c = HW; is.h = W; is.w = 1;
-        const float *img1 = pair + (long)C * HW;
-        constexpr int TW = 64;
-        const int tiles_x = (W + TW - 1) / TW;
-#define FN2_WF(TH)                                                                                                      \
-    do {                                                                                                                \
-        const int tiles_y = (H + TH - 1) / TH;                                                                          \
-        hipLaunchKernelGGL((resample_fwd_tiled<TH, TW, 16, 1>), dim3((unsigned)((long)B * tiles_x * tiles_y)),          \
-                           dim3(1024), 0, s, img1, is, flow, out, C, H, W, H, W, tiles_x, tiles_y, (bilinear & 1) ? 1 : 0, \
-                           pair, div_flow);                                                                             \
-    } while (0)
-        if (tile_height(B, H, tiles_x) == 48) FN2_WF(48); else FN2_WF(32);
-#undef FN2_WF
+    ImgStrides is;
+    const float *img1 = pair_second(pair, C, H, W, is);
+    if (tiled_shape_ok(is, img1, H, W, H, W)) {
+        launch_fwd_tiled<FUSE>(img1, is, flow, out, B, C, H, W, bilinear, pair, div_flow, s);
     } else {
-        hipLaunchKernelGGL(warp_diff_norm_cat_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out, C, H, W,
-                           npix, (bilinear & 1) ? 1 : 0, div_flow, 0);
+        const long npix = (long)B * H * W;
+        hipLaunchKernelGGL(warp_diff_norm_cat_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out, C, H, W, npix, bilinear,
+                           div_flow, FUSE == 2 ? 1 : 0);
     }
     return launch_status();
 }
 
-// shapes resample_bwd_c3x takes (the tiled path's conditions, three channels)
-static bool c3x_ok(fn2::ImgStrides is, const float *img, int C, int Hi, int Wi, int H, int W)
+extern "C" int fn2_warp_diff_norm_cat(const float *pair, const float *flow, float *out, float div_flow,
+                                      int B, int C, int H, int W, int bilinear, void *stream)
 {
-    return C == 3 && (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && fn2::aligned(img, 16) && (Hi == H) &&
-           (Wi == W) && (W % 4 == 0) && (H >= 16) && (W >= 32);
+    return warp_diff_norm_forward<1>(pair, flow, out, div_flow, B, C, H, W, bilinear, stream);
+}
+
+extern "C" int fn2_warp_diff_norm(const float *pair, const float *flow, float *out_norm, int B, int C, int H, int W, int bilinear, void *stream)
+{
+    return warp_diff_norm_forward<2>(pair, flow, out_norm, 1.0f, B, C, H, W, bilinear, stream);
 }
 
 extern "C" int fn2_warp_diff_norm_cat_backward(const float *pair, const float *flow, const float *out_cat, const float *grad_cat,
                                                float *grad_pair, float *grad_flow, float div_flow, int B, int C, int H, int W,
                                                int bilinear, void *stream)
 {
-    using namespace fn2;
     (void)bilinear;   // both reference backward kernels ignore the flag (resample2d_kernel.cu:75-198)
-    if (B < 0 || C < 1 || H < 1 || W < 1 || !(div_flow == div_flow) || div_flow == 0.0f) return FN2_EINVAL;
+    if (pair_dims_bad(B, C, H, W, div_flow)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!pair || !flow || !out_cat || !grad_cat || !grad_flow) return FN2_EINVAL;
-    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(out_cat, 4) || !aligned(grad_cat, 4) || !aligned(grad_flow, 4) ||
-        (grad_pair && !aligned(grad_pair, 4)))
-        return FN2_EALIGN;
+    if (any_null(pair, flow, out_cat, grad_cat, grad_flow)) return FN2_EINVAL;
+    if (!all_aligned(4, pair, flow, out_cat, grad_cat, grad_flow, grad_pair)) return FN2_EALIGN;   // grad_pair may be null
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long HW = (long)H * W, npix = (long)B * HW;
     const float inv = 1.0f / div_flow;
-    if (grad_pair) {   // the second image's gradient starts as its slice of the concat gradient (one strided copy), then the scatter adds
-        hipError_t e = hipMemcpy2DAsync(grad_pair + (long)C * HW, 2 * C * HW * sizeof(float), grad_cat + (long)C * HW,
-                                        (3 * C + 3) * HW * sizeof(float), C * HW * sizeof(float), B, hipMemcpyDeviceToDevice, s);
+    if (grad_pair) {
+        hipError_t e = seed_second_grad(grad_pair, grad_cat, B, C, HW, s);
         if (e != hipSuccess) return (int)e;
     }
     ImgStrides is;
-    is.b = 2L * C * HW; is.c = HW; is.h = W; is.w = 1;
-    const float *img1 = pair + (long)C * HW;
-    if (c3x_ok(is, img1, C, H, W, H, W)) {
-        C3xArgs a = c3x_args(img1, is, flow, grad_pair ? grad_pair + 3 * HW : nullptr, 6 * HW, grad_flow, B, H, W, H, W, (W + 63) / 64, 0);
+    const float *img1 = pair_second(pair, C, H, W, is);
+    if (C == 3 && tiled_shape_ok(is, img1, H, W, H, W)) {
+        C3xArgs a = c3x_args(img1, is, flow, grad_pair ? grad_pair + 3 * HW : nullptr, 6 * HW, grad_flow, B, H, W, H, W, 0);
         a.gcat = grad_cat; a.pair = pair; a.outcat = out_cat; a.gpair0 = grad_pair; a.inv_div_flow = inv;
-        if (grad_pair) hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, 1, true>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
-        else hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, 1, false>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
-        return launch_status();
-    }
-    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_cat, grad_cat, grad_pair,
-                       grad_flow, C, H, W, npix, inv, 0, 1);
-    return launch_status();
-}
-
-// models.py:157-161 / :170-174: ||pair[:, :C] - Resample2d(pair[:, C:], flow)||_2 with no concat -- row N2's forward kernel storing
-// only the norm plane
-extern "C" int fn2_warp_diff_norm(const float *pair, const float *flow, float *out_norm, int B, int C, int H, int W, int bilinear, void *stream)
-{
-    using namespace fn2;
-    bilinear = bilinear != 0 ? 1 : 0;
-    if (B < 0 || C < 1 || H < 1 || W < 1) return FN2_EINVAL;
-    if ((long)B * H * W == 0) return FN2_OK;
-    if (!pair || !flow || !out_norm) return FN2_EINVAL;
-    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(out_norm, 4)) return FN2_EALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W, npix = (long)B * HW;
-    if ((W % 4 == 0) && aligned(pair, 16) && (H >= 16) && (W >= 32)) {
-        ImgStrides is;
-        is.b = 2 * C * HW; is.c = HW; is.h = W; is.w = 1;
-        const float *img1 = pair + (long)C * HW;
-        const int tiles_x = (W + 63) / 64;
-#define FN2_WN(TH)                                                                                                      \
-    do {                                                                                                                \
-        const int tiles_y = (H + TH - 1) / TH;                                                                          \
-        hipLaunchKernelGGL((resample_fwd_tiled<TH, 64, 16, 2>), dim3((unsigned)((long)B * tiles_x * tiles_y)),          \
-                           dim3(1024), 0, s, img1, is, flow, out_norm, C, H, W, H, W, tiles_x, tiles_y, bilinear, pair, 1.0f); \
-    } while (0)
-        if (tile_height(B, H, tiles_x) == 48) FN2_WN(48); else FN2_WN(32);
-#undef FN2_WN
+        if (grad_pair) launch_c3x<1, true>(a, s);
+        else launch_c3x<1, false>(a, s);
     } else {
-        hipLaunchKernelGGL(warp_diff_norm_cat_kernel, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_norm, C, H, W, npix,
-                           bilinear, 1.0f, 1);
+        hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, out_cat, grad_cat,
+                           grad_pair, grad_flow, C, H, W, npix, inv, 0, 1);
     }
     return launch_status();
 }
 
-// ... and its backward with respect to the flow (the pair is the network's input in FlowNet2; compose the unfused entry points when it
-// needs a gradient): grad_flow = Resample2d's flow gradient for g_warped = -grad_norm * diff / (norm + 1e-9), the warp recomputed
+// fn2_warp_diff_norm's backward with respect to the flow (the pair is the network's input in FlowNet2; compose the unfused entry points
+// when it needs a gradient): grad_flow = Resample2d's flow gradient for g_warped = -grad_norm * diff / (norm + 1e-9), the warp recomputed
 extern "C" int fn2_warp_diff_norm_backward(const float *pair, const float *flow, const float *norm, const float *grad_norm,
                                            float *grad_flow, int B, int C, int H, int W, int bilinear, void *stream)
 {
-    using namespace fn2;
     bilinear = bilinear != 0 ? 1 : 0;
-    if (B < 0 || C < 1 || H < 1 || W < 1) return FN2_EINVAL;
+    if (pair_dims_bad(B, C, H, W)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!pair || !flow || !norm || !grad_norm || !grad_flow) return FN2_EINVAL;
-    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(norm, 4) || !aligned(grad_norm, 4) || !aligned(grad_flow, 4)) return FN2_EALIGN;
+    if (any_null(pair, flow, norm, grad_norm, grad_flow)) return FN2_EINVAL;
+    if (!all_aligned(4, pair, flow, norm, grad_norm, grad_flow)) return FN2_EALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W, npix = (long)B * HW;
     ImgStrides is;
-    is.b = 2L * C * HW; is.c = HW; is.h = W; is.w = 1;
-    const float *img1 = pair + (long)C * HW;
-    if (c3x_ok(is, img1, C, H, W, H, W)) {
-        C3xArgs a = c3x_args(img1, is, flow, nullptr, 0, grad_flow, B, H, W, H, W, (W + 63) / 64, 0);
+    const float *img1 = pair_second(pair, C, H, W, is);
+    if (C == 3 && tiled_shape_ok(is, img1, H, W, H, W)) {
+        C3xArgs a = c3x_args(img1, is, flow, nullptr, 0, grad_flow, B, H, W, H, W, 0);
         a.gcat = grad_norm; a.pair = pair; a.outcat = norm; a.bilinear = bilinear;
-        hipLaunchKernelGGL((resample_bwd_c3x<32, 64, 16, 1024, 2, false>), dim3(c3x_grid(a)), dim3(1024), 0, s, a);
-        return launch_status();
+        launch_c3x<2, false>(a, s);
+    } else {
+        const long npix = (long)B * H * W;
+        hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, norm, grad_norm,
+                           static_cast<float *>(nullptr), grad_flow, C, H, W, npix, 0.0f, 1, bilinear);
     }
-    hipLaunchKernelGGL(warp_diff_norm_cat_bwd_kernel<false>, dim3(stream_grid(npix)), dim3(256), 0, s, pair, flow, norm, grad_norm,
-                       static_cast<float *>(nullptr), grad_flow, C, H, W, npix, 0.0f, 1, bilinear);
     return launch_status();
 }
 
@@ -2000,9 +1886,8 @@ static int det_K(int ks, int H, int W)
 
 // clear the workspace and find the plane maxima (the first two steps of every deterministic call)
 template <int MODE>
-static int det_begin(const fn2::DetSrc &d, int B, void *workspace, size_t bytes, fn2::DetAcc &det, int K, hipStream_t s)
+static int det_begin(const DetSrc &d, int B, void *workspace, size_t bytes, DetAcc &det, int K, hipStream_t s)
 {
-    using namespace fn2;
     const long planes = (long)B * d.C;
     hipError_t e = hipMemsetAsync(workspace, 0, bytes, s);
     if (e != hipSuccess) return (int)e;
@@ -2019,10 +1904,9 @@ static int det_begin(const fn2::DetSrc &d, int B, void *workspace, size_t bytes,
 
 // the conversion of the finite planes and the serial scatter of the non-finite ones, in one launch
 template <int MODE>
-static void det_end(const fn2::DetSrc &d, const float *flow, const fn2::DetAcc &det, float *G0, long g_bs, int B, int Hi, int Wi, int H,
-                    int W, int ks, hipStream_t s)
+static void det_end(const DetSrc &d, const float *flow, const DetAcc &det, float *G0, long g_bs, int B, int Hi, int Wi, int H, int W, int ks,
+                    hipStream_t s)
 {
-    using namespace fn2;
     const long planes = (long)B * d.C, HWi = (long)Hi * Wi;
     if (planes == 0) return;
     const unsigned ncvt = stream_grid(planes * HWi), nfb = (unsigned)((planes + 255) / 256);
@@ -2032,7 +1916,7 @@ static void det_end(const fn2::DetSrc &d, const float *flow, const fn2::DetAcc &
 
 extern "C" size_t fn2_resample2d_backward_det_workspace_bytes(int B, int C, int Hi, int Wi, int H, int W, int kernel_size)
 {
-    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0 || kernel_size < 1) return 0;
+    if (resample_dims_bad(B, C, Hi, Wi, H, W, kernel_size)) return 0;
     return det_workspace_bytes((long)B * C, (long)Hi * Wi);
 }
 
@@ -2041,20 +1925,14 @@ extern "C" int fn2_resample2d_backward_det(const float *img, const int64_t *img_
                                            int B, int C, int Hi, int Wi, int H, int W,
                                            int kernel_size, int bilinear, void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace fn2;
     (void)bilinear;   // both reference backward kernels ignore the flag
-    if (B < 0 || C < 0 || Hi < 1 || Wi < 1 || H < 0 || W < 0) return FN2_EINVAL;
-    if (kernel_size < 1) return FN2_EINVAL;
+    if (resample_dims_bad(B, C, Hi, Wi, H, W, kernel_size)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!img || !flow || !grad_out || !grad_img || !grad_flow) return FN2_EINVAL;
+    if (any_null(img, flow, grad_out, grad_img, grad_flow)) return FN2_EINVAL;
     const size_t need = det_workspace_bytes((long)B * C, (long)Hi * Wi);
     if (!workspace || workspace_bytes < need) return FN2_EINVAL;
-    if (!aligned(img, 4) || !aligned(flow, 4) || !aligned(grad_out, 4) || !aligned(grad_img, 4) || !aligned(grad_flow, 4) ||
-        !aligned(workspace, 8))
-        return FN2_EALIGN;
-    ImgStrides is;
-    if (img_strides) { is.b = img_strides[0]; is.c = img_strides[1]; is.h = img_strides[2]; is.w = img_strides[3]; }
-    else { is.b = (long)C * Hi * Wi; is.c = (long)Hi * Wi; is.h = Wi; is.w = 1; }
+    if (!all_aligned(4, img, flow, grad_out, grad_img, grad_flow) || !aligned(workspace, 8)) return FN2_EALIGN;
+    const ImgStrides is = dense_or(img_strides, C, Hi, Wi);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long npix = (long)B * H * W;
     DetSrc d{};
@@ -2064,15 +1942,13 @@ extern "C" int fn2_resample2d_backward_det(const float *img, const int64_t *img_
     if (rc != FN2_OK) return rc;
     // the atomic path's kernels with the scatter turned into fixed-point adds (same gather, same grad_flow); the tiled shapes take the
     // per-channel LDS-window kernel for every C, its window cells int64 instead of fp64
-    const bool tiled_ok = (is.w == 1) && (is.h % 4 == 0) && (is.c % 4 == 0) && (is.b % 4 == 0) && aligned(img, 16) &&
-                          (Hi == H) && (Wi == W) && (W % 4 == 0) && (H >= 16) && (W >= 32);
     if (kernel_size != 1) {
         hipLaunchKernelGGL(resample_bwd_ks_kernel<true>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
                            grad_flow, C, Hi, Wi, H, W, npix, kernel_size, det);
-    } else if (tiled_ok) {
+    } else if (tiled_shape_ok(is, img, Hi, Wi, H, W)) {
         const int tiles_x = (W + 63) / 64, tiles_y = (H + 31) / 32;
-        hipLaunchKernelGGL((resample_bwd_tiled<32, 64, 16, 1024, 8, 2>), dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(1024), 0, s,
-                           img, is, flow, grad_out, grad_img, grad_flow, C, Hi, Wi, H, W, tiles_x, tiles_y, 0, det);
+        hipLaunchKernelGGL((resample_bwd_tiled<32, 64, 16, 1024, 8, 2>), tile_grid(B, tiles_x, tiles_y), dim3(1024), 0, s, img, is, flow,
+                           grad_out, grad_img, grad_flow, C, Hi, Wi, H, W, tiles_x, tiles_y, 0, det);
     } else {
         hipLaunchKernelGGL(resample_bwd_kernel<true>, dim3(stream_grid(npix)), dim3(256), 0, s, img, is, flow, grad_out, grad_img,
                            grad_flow, C, Hi, Wi, H, W, npix, det);
@@ -2083,7 +1959,7 @@ extern "C" int fn2_resample2d_backward_det(const float *img, const int64_t *img_
 
 extern "C" size_t fn2_warp_diff_norm_cat_backward_det_workspace_bytes(int B, int C, int H, int W)
 {
-    if (B < 0 || C < 1 || H < 1 || W < 1) return 0;
+    if (pair_dims_bad(B, C, H, W)) return 0;
     return det_workspace_bytes((long)B * C, (long)H * W);
 }
 
@@ -2091,23 +1967,18 @@ extern "C" int fn2_warp_diff_norm_cat_backward_det(const float *pair, const floa
                                                    float *grad_pair, float *grad_flow, float div_flow, int B, int C, int H, int W,
                                                    int bilinear, void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace fn2;
-    if (B < 0 || C < 1 || H < 1 || W < 1 || !(div_flow == div_flow) || div_flow == 0.0f) return FN2_EINVAL;
+    if (pair_dims_bad(B, C, H, W, div_flow)) return FN2_EINVAL;
     if ((long)B * H * W == 0) return FN2_OK;
-    if (!pair || !flow || !out_cat || !grad_cat || !grad_flow) return FN2_EINVAL;
+    if (any_null(pair, flow, out_cat, grad_cat, grad_flow)) return FN2_EINVAL;
     const size_t need = det_workspace_bytes((long)B * C, (long)H * W);
     if (!workspace || workspace_bytes < need) return FN2_EINVAL;
     if (!aligned(workspace, 8)) return FN2_EALIGN;
     // no pair gradient: nothing is scattered, the existing entry point is already deterministic
     if (!grad_pair) return fn2_warp_diff_norm_cat_backward(pair, flow, out_cat, grad_cat, nullptr, grad_flow, div_flow, B, C, H, W, bilinear, stream);
-    if (!aligned(pair, 4) || !aligned(flow, 4) || !aligned(out_cat, 4) || !aligned(grad_cat, 4) || !aligned(grad_flow, 4) ||
-        !aligned(grad_pair, 4))
-        return FN2_EALIGN;
+    if (!all_aligned(4, pair, flow, out_cat, grad_cat, grad_flow, grad_pair)) return FN2_EALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long HW = (long)H * W, npix = (long)B * HW;
-    // the second image's gradient starts as its slice of the concat gradient, as on the atomic path
-    hipError_t e = hipMemcpy2DAsync(grad_pair + (long)C * HW, 2 * C * HW * sizeof(float), grad_cat + (long)C * HW,
-                                    (3 * C + 3) * HW * sizeof(float), C * HW * sizeof(float), B, hipMemcpyDeviceToDevice, s);
+    hipError_t e = seed_second_grad(grad_pair, grad_cat, B, C, HW, s);   // as on the atomic path
     if (e != hipSuccess) return (int)e;
     DetSrc d{};
     d.gcat = grad_cat; d.pair = pair; d.outcat = out_cat; d.C = C; d.HW = HW;

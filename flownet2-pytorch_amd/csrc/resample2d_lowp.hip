@@ -84,33 +84,6 @@ struct Warp16Args {
     float inv_div_flow;
 };
 
-// The sampling position of one pixel: the forward's corners and weights (resample_fwd_kernel) -- in nearest mode all four corners are
-// the nearest pixel -- or, BWD, the corners the flow gradient gathers (always the bilinear ones, resample_bwd_kernel).
-struct WarpPos { int xL, xR, yT, yB; float alpha, beta; };
-template <bool BWD> __device__ __forceinline__ WarpPos warp_pos(int x, int y, float dx, float dy, int H, int W, int bilinear)
-{
-    WarpPos q;
-    const float xf = (float)x + dx, yf = (float)y + dy;
-    const float fx = floorf(xf), fy = floorf(yf);
-    q.alpha = xf - fx; q.beta = yf - fy;
-    if (BWD || bilinear) {
-        q.xL = clampi(f2i_sat(fx), 0, W - 1); q.xR = clampi(f2i_sat(fx + 1.0f), 0, W - 1);
-        q.yT = clampi(f2i_sat(fy), 0, H - 1); q.yB = clampi(f2i_sat(fy + 1.0f), 0, H - 1);
-    } else {
-        q.xL = q.xR = clampi(d2i_sat(floor((double)xf + 0.5)), 0, W - 1);
-        q.yT = q.yB = clampi(d2i_sat(floor((double)yf + 0.5)), 0, H - 1);
-    }
-    return q;
-}
-// the forward's value from the gathered corners.  Backward, nearest mode: the nearest pixel is the corner alpha / beta >= 0.5 select
-// (floor(xf + 0.5) = floor(xf) + (alpha >= 0.5), clamped like the corner), as resample_bwd_c3x recomputes it.
-template <bool BWD> __device__ __forceinline__ float warp_value(const WarpPos &q, int bilinear, float i00, float i01, float i10, float i11)
-{
-    if (bilinear) return bilinear_sample(q.alpha, q.beta, i00, i01, i10, i11);
-    if (!BWD) return i00;
-    return q.alpha >= 0.5f ? (q.beta >= 0.5f ? i11 : i01) : (q.beta >= 0.5f ? i10 : i00);
-}
-
 template <class T, int MODE>
 __global__ __launch_bounds__(256) void warp16_tiled(const Warp16Args p)
 {
@@ -355,9 +328,7 @@ template <class T, int MODE> static int warp16_launch(const fn2::Warp16Args &a, 
         hipLaunchKernelGGL((warp16_tiled<T, MODE>), dim3((unsigned)((long)a.B * a.tiles_x * a.tiles_y)), dim3(256), 0, s, a);
     } else {
         const long npix = (long)a.B * a.H * a.W;
-        long blocks = (npix + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL((warp16_pixel<T, MODE>), dim3((unsigned)blocks), dim3(256), 0, s, a, npix);
+        hipLaunchKernelGGL((warp16_pixel<T, MODE>), dim3(stream_grid(npix)), dim3(256), 0, s, a, npix);
     }
     return launch_status();
 }

@@ -97,6 +97,76 @@ def test_rejected_calls_return_codes_without_gpu():
     assert ml(outs, p, p, None, w1, f32(1.0), 2, 1, 8, 8, 4, 1, f32(0.05), p, ctypes.c_size_t(0), null) == -1          # workspace too small
 
 
+def test_float32_warp_entry_points_check_in_a_fixed_order():
+    """Calls in which two checks of a float32 warp entry point disagree: dims and kernel_size (with div_flow) first, then empty -> FN2_OK,
+    null -> FN2_EINVAL, (det) workspace -> FN2_EINVAL, alignment -> FN2_EALIGN.  Every call returns before any launch."""
+    lib = fn2_capi.lib()
+    OK, EINVAL, EALIGN = 0, -1, -3
+    f32, sz = ctypes.c_float, ctypes.c_size_t
+    null = ctypes.c_void_p(0)
+    buf = (ctypes.c_char * 4096)()
+    base = (ctypes.addressof(buf) + 15) // 16 * 16
+    p, mis = ctypes.c_void_p(base), ctypes.c_void_p(base + 2)
+    ws, ws_mis = ctypes.c_void_p(base + 1024), ctypes.c_void_p(base + 1024 + 4)   # 8-byte aligned / only 4-byte aligned
+    nan = f32(float("nan"))
+
+    def dims(B, ks=None):   # B x 1 x 2 x 2, image of the flow's size
+        return (B, 1, 2, 2, 2, 2) + (() if ks is None else (ks,))
+
+    def pdims(B):           # the pair entry points: B, C, H, W
+        return (B, 1, 2, 2)
+
+    need = lib.fn2_resample2d_backward_det_workspace_bytes(*dims(1, 1))
+    pneed = lib.fn2_warp_diff_norm_cat_backward_det_workspace_bytes(*pdims(1))
+    assert 0 < need <= 1024 and 0 < pneed <= 1024
+    fwd, bwd, bdet = lib.fn2_resample2d_forward, lib.fn2_resample2d_backward, lib.fn2_resample2d_backward_det
+    cat, cbwd, cdet = lib.fn2_warp_diff_norm_cat, lib.fn2_warp_diff_norm_cat_backward, lib.fn2_warp_diff_norm_cat_backward_det
+    nrm, nbwd = lib.fn2_warp_diff_norm, lib.fn2_warp_diff_norm_backward
+    d20 = f32(20.0)
+    table = [
+        # B = 0 with null pointers: the empty check comes before the null check
+        ("fwd empty", fwd, (null, null, null, null) + dims(0, 1) + (1, null), OK),
+        ("bwd empty", bwd, (null, null, null, null, null, null) + dims(0, 1) + (1, null), OK),
+        ("bdet empty", bdet, (null, null, null, null, null, null) + dims(0, 1) + (1, null, sz(0), null), OK),
+        ("cat empty", cat, (null, null, null, d20) + pdims(0) + (1, null), OK),
+        ("cbwd empty", cbwd, (null, null, null, null, null, null, d20) + pdims(0) + (1, null), OK),
+        ("cdet empty", cdet, (null, null, null, null, null, null, d20) + pdims(0) + (1, null, sz(0), null), OK),
+        ("nrm empty", nrm, (null, null, null) + pdims(0) + (1, null), OK),
+        ("nbwd empty", nbwd, (null, null, null, null, null) + pdims(0) + (1, null), OK),
+        # B = 0 with kernel_size = 0: kernel_size comes before the empty check
+        ("fwd empty ks", fwd, (p, null, p, p) + dims(0, 0) + (1, null), EINVAL),
+        ("bwd empty ks", bwd, (p, null, p, p, p, p) + dims(0, 0) + (1, null), EINVAL),
+        ("bdet empty ks", bdet, (p, null, p, p, p, p) + dims(0, 0) + (1, ws, sz(1024), null), EINVAL),
+        # div_flow = NaN with B = 0: div_flow is checked with the dims
+        ("cat empty nan", cat, (p, p, p, nan) + pdims(0) + (1, null), EINVAL),
+        ("cbwd empty nan", cbwd, (p, p, p, p, p, p, nan) + pdims(0) + (1, null), EINVAL),
+        ("cdet empty nan", cdet, (p, p, p, p, p, p, nan) + pdims(0) + (1, ws, sz(1024), null), EINVAL),
+        # a null pointer together with a misaligned one: null comes before alignment
+        ("fwd null mis", fwd, (mis, null, p, null) + dims(1, 1) + (1, null), EINVAL),
+        ("bwd null mis", bwd, (mis, null, p, p, p, null) + dims(1, 1) + (1, null), EINVAL),
+        ("bdet null mis", bdet, (mis, null, p, p, p, null) + dims(1, 1) + (1, ws, sz(1024), null), EINVAL),
+        ("cat null mis", cat, (mis, p, null, d20) + pdims(1) + (1, null), EINVAL),
+        ("cbwd null mis", cbwd, (mis, p, p, p, p, null, d20) + pdims(1) + (1, null), EINVAL),
+        ("cdet null mis", cdet, (mis, p, p, p, p, null, d20) + pdims(1) + (1, ws, sz(1024), null), EINVAL),
+        ("nrm null mis", nrm, (mis, p, null) + pdims(1) + (1, null), EINVAL),
+        ("nbwd null mis", nbwd, (mis, p, p, p, null) + pdims(1) + (1, null), EINVAL),
+        # det: a workspace that is too small together with a misaligned pointer: the workspace comes before alignment
+        ("bdet small ws mis", bdet, (mis, null, p, p, p, p) + dims(1, 1) + (1, ws, sz(need - 1), null), EINVAL),
+        ("cdet small ws mis", cdet, (mis, p, p, p, p, p, d20) + pdims(1) + (1, ws, sz(pneed - 1), null), EINVAL),
+        ("bdet no ws mis", bdet, (mis, null, p, p, p, p) + dims(1, 1) + (1, null, sz(1024), null), EINVAL),
+        ("cdet no ws mis", cdet, (mis, p, p, p, p, p, d20) + pdims(1) + (1, null, sz(1024), null), EINVAL),
+        # det: a misaligned workspace of sufficient size
+        ("bdet ws mis", bdet, (p, null, p, p, p, p) + dims(1, 1) + (1, ws_mis, sz(1024), null), EALIGN),
+        ("cdet ws mis", cdet, (p, p, p, p, p, p, d20) + pdims(1) + (1, ws_mis, sz(1024), null), EALIGN),
+        # the concat row's det call without a pair gradient hands over to the atomic entry point only after its own workspace check
+        ("cdet no grad_pair small ws", cdet, (p, p, p, p, null, p, d20) + pdims(1) + (1, ws, sz(pneed - 1), null), EINVAL),
+        ("cdet no grad_pair no ws", cdet, (p, p, p, p, null, p, d20) + pdims(1) + (1, null, sz(1024), null), EINVAL),
+        ("cdet no grad_pair ws mis", cdet, (p, p, p, p, null, p, d20) + pdims(1) + (1, ws_mis, sz(1024), null), EALIGN),
+    ]
+    for what, fn, args, want in table:
+        assert fn(*args) == want, what
+
+
 def test_modules_keep_reference_names_and_signatures():
     import channelnorm_cuda
     import correlation_cuda
