@@ -63,7 +63,7 @@ struct MultiScaleOp : public torch::autograd::Function<MultiScaleOp> {
         const char *op = "multiscale_loss_cuda.apply";
         const int n = (int)outputs.size();
         check_gpu(target_, op, "target");
-        TORCH_CHECK(n >= 1 && n <= 6 && (int)weights.size() == n, op, ": 1..6 predictions with one weight each expected, got ", n, " / ", weights.size());
+        TORCH_CHECK(n >= 1 && n <= 5 && (int)weights.size() == n, op, ": 1..5 predictions with one weight each expected, got ", n, " / ", weights.size());
         TORCH_CHECK(target_.dim() == 4 && target_.size(1) == 2 && target_.scalar_type() == at::kFloat, op, ": target must be float32 B x 2 x H x W, got ",
                     target_.sizes());
         TORCH_CHECK(norm == 1 || norm == 2, op, ": norm must be 1 (L1) or 2 (L2)");
@@ -153,7 +153,7 @@ at::Tensor multiscale_sums(const at::Tensor &target, std::vector<at::Tensor> out
     const char *op = "multiscale_loss_cuda.sums";
     const int n = (int)outputs.size();
     check_gpu(target, op, "target");
-    TORCH_CHECK(n >= 1 && n <= 6, op, ": 1..6 predictions expected");
+    TORCH_CHECK(n >= 1 && n <= 5, op, ": 1..5 predictions expected");
     c10::DeviceGuard guard(target.device());
     at::Tensor t = target.contiguous();
     std::vector<at::Tensor> outs(n);

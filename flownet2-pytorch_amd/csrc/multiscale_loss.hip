@@ -247,7 +247,7 @@ extern "C" size_t fn2_multiscale_workspace_bytes(int B, int H, int W, int start_
 {
     int kmax, bx, by;
     if (ms_geometry(B, H, W, start_scale, num_scales, &kmax, &bx, &by) != FN2_OK) return 0;
-    return ms_partial_bytes(B, bx, by, num_scales) + 64;       // partial sums + the ticket counter (its own 64-byte line)
+    return ms_partial_bytes(B, bx, by, num_scales) + 64;       // the ticket counter (its own 64-byte line) + partial sums
 }
 
 static int ms_launch(const float *const *outputs, const float *target, float *sums, float *loss_epe, float *const *grads,
@@ -258,12 +258,16 @@ static int ms_launch(const float *const *outputs, const float *target, float *su
     MsArgs a;
     int rc = ms_geometry(B, H, W, start_scale, num_scales, &a.kmax, &a.bx, &a.by);
     if (rc != FN2_OK) return rc;
-    if (!outputs || !target || !sums || !workspace || (norm != 1 && norm != 2)) return FN2_EINVAL;
+    const int nblocks = B * a.bx * a.by;
+    // (an empty batch has no target elements: its tensor may come as a null pointer, like a level without elements below)
+    if (!outputs || (!target && nblocks > 0) || !sums || !workspace || (norm != 1 && norm != 2)) return FN2_EINVAL;
     if (workspace_bytes < fn2_multiscale_workspace_bytes(B, H, W, start_scale, num_scales)) return FN2_EINVAL;
     if (!aligned(target, 4) || !aligned(sums, 4) || !aligned(workspace, 4) || (loss_epe && !aligned(loss_epe, 4))) return FN2_EALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    a.target = target; a.partial = static_cast<float *>(workspace);
-    a.ticket = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + ms_partial_bytes(B, a.bx, a.by, num_scales));
+    // the ticket counter comes first, where every geometry finds it: a primed workspace stays primed for any call that fits it (behind
+    // the partial sums it would sit where an earlier call of another geometry left partial sums)
+    a.target = target; a.ticket = static_cast<unsigned *>(workspace);
+    a.partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + 64);
     a.sums = sums; a.loss_epe = loss_epe;
     a.B = B; a.H = H; a.W = W; a.s0 = start_scale; a.ns = num_scales; a.div_flow = div_flow; a.norm = norm;
     a.vec4 = (W % 4 == 0) && aligned(target, 16);
@@ -281,7 +285,6 @@ static int ms_launch(const float *const *outputs, const float *target, float *su
         a.coef[i] = (weights && px > 0) ? (float)((double)weights[i] / (2.0 * px)) : 0.0f;
         a.coef[num_scales + i] = (weights && px > 0) ? (float)((double)weights[i] / px) : 0.0f;
     }
-    const int nblocks = B * a.bx * a.by;
     if (nblocks == 0) {   // empty batch: every sum is zero
         hipError_t e = hipMemsetAsync(sums, 0, 2 * num_scales * sizeof(float), s);
         if (e == hipSuccess && loss_epe) e = hipMemsetAsync(loss_epe, 0, 2 * sizeof(float), s);

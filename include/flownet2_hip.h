@@ -388,7 +388,10 @@ int fn2_warp_diff_norm_backward_16(const void *pair, const void *flow, const voi
  *   weights    : host array of num_scales loss weights (only used for grads)
  *   workspace  : device scratch of fn2_multiscale_workspace_bytes(...) bytes (per-workgroup partial sums and a ticket counter:
  *                the last workgroup to finish adds the partial sums in a fixed order -- the result is deterministic)
- * float32. */
+ * float32.  Rejected before anything is launched: num_scales < 1 or > 6, start_scale < 1 or not a power of two, B < 0, H or W < 1, a
+ * NULL outputs / sums / workspace (target: unless B == 0; outputs[i]: unless level i has no elements), a workspace smaller than
+ * fn2_multiscale_workspace_bytes(...), norm not 1 or 2: FN2_EINVAL.  start_scale > 16 or k_max / start_scale > 16 (so num_scales == 6
+ * whatever the start_scale): FN2_EUNSUPPORTED.  fn2_multiscale_workspace_bytes returns 0 for both.  B == 0: every sum is 0. */
 size_t fn2_multiscale_workspace_bytes(int B, int H, int W, int start_scale, int num_scales);
 int fn2_multiscale_l1_epe(const float *const *outputs, const float *target, float *sums, float *const *grads,
                           const float *weights, float grad_scale, int B, int H, int W, int start_scale, int num_scales,
@@ -404,11 +407,11 @@ int fn2_multiscale_loss(const float *const *outputs, const float *target, float 
 /* Row N3 as the autograd node uses it (ABI v3): the same pass, with the weighted means themselves written by the kernel --
  *   loss_epe[0] = sum_i weights[i] * L_i   (norm 1: L_i = sums[i] / (B*2*H_i*W_i); norm 2: L_i = sums[n+i] / (B*H_i*W_i), losses.py:21-26)
  *   loss_epe[1] = sum_i weights[i] * sums[n+i] / (B*H_i*W_i)                                               (losses.py:77)
- * -- by the last workgroup to finish (a ticket counter at the end of `workspace`; the summation order is fixed, the result
+ * -- by the last workgroup to finish (a ticket counter in the first 64 bytes of `workspace`, the same place for every geometry; the summation order is fixed, the result
  * deterministic), so that loss and metric cost ONE launch.  workspace_primed != 0: the caller guarantees that the workspace was
  * zero-filled once and has since only been used by this entry point on one stream at a time (the kernel leaves the counter at
- * zero); 0: the counter is cleared by a 4-byte memset node in front of the kernel (any scratch memory will do).  `weights` is
- * required. */
+ * zero) -- for any geometry that fits it, not only the one it was first used with; 0: the counter is cleared by a 4-byte memset
+ * node in front of the kernel (any scratch memory will do).  `weights` and `loss_epe` are required: FN2_EINVAL without them. */
 int fn2_multiscale_loss_fused(const float *const *outputs, const float *target, float *sums, float *loss_epe, float *const *grads,
                               const float *weights, float grad_scale, int norm, int B, int H, int W, int start_scale, int num_scales,
                               float div_flow, void *workspace, size_t workspace_bytes, int workspace_primed, void *stream);
