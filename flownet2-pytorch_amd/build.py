@@ -1,5 +1,6 @@
 """Builds libflownet2_hip.so (hand-written gfx950 HIP kernels + C ABI) and the three pybind
-modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without hipify.
+modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without hipify; and libflownet2_hip_ext.so
+(include/flownet2_hip_ext.h: layers outside the drop-in boundary, Correlation1d) with its module correlation1d_cuda.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -22,7 +23,11 @@ KERNEL_SRCS = ["capi.hip", "channelnorm.hip", "resample2d.hip", "resample2d_lowp
                "multiscale_loss.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              "-munsafe-fp-atomics", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
-MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda"]
+# libflownet2_hip_ext.so: a sibling library of its own (csrc/exports_ext.map), self-contained -- it does not link libflownet2_hip.so
+EXT_LIB = os.path.join(LIBDIR, "libflownet2_hip_ext.so")
+EXT_SRCS = ["capi_ext.hip", "correlation_1d.hip"]
+MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda"]
+MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext"}   # every other module links libflownet2_hip.so
 
 
 def _newer(target, deps):
@@ -40,16 +45,20 @@ def _run(cmd):
     return r
 
 
-def build_lib(force=False, debug=False):
+def build_lib(force=False, debug=False, ext=False):
     """libflownet2_hip.so (the product: public C ABI only) or, with debug=True, libflownet2_hip_debug.so: the same kernels plus
-    the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs)."""
-    objdir = os.path.join(LIBDIR, "debug") if debug else LIBDIR
-    lib = os.path.join(LIBDIR, "libflownet2_hip_debug.so") if debug else LIB
+    the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs);
+    with ext=True libflownet2_hip_ext.so (EXT_SRCS, the same flags, its own version script)."""
+    objdir = os.path.join(LIBDIR, "ext") if ext else os.path.join(LIBDIR, "debug") if debug else LIBDIR
+    lib = EXT_LIB if ext else os.path.join(LIBDIR, "libflownet2_hip_debug.so") if debug else LIB
+    vmap = os.path.join(CSRC, "exports_ext.map" if ext else "exports.map")
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip.h"))
+    if ext:
+        hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"))
     objs, jobs = [], []
-    for src in KERNEL_SRCS:
+    for src in (EXT_SRCS if ext else KERNEL_SRCS):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         if force or not _newer(o, [s] + hdrs):
@@ -59,8 +68,8 @@ def build_lib(force=False, debug=False):
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
             list(pool.map(_run, jobs))
-    if force or not _newer(lib, objs + [os.path.join(CSRC, "exports.map")]):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", lib] + objs)
+    if force or not _newer(lib, objs + [vmap]):
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + vmap, "-o", lib] + objs)
     return lib
 
 
@@ -74,7 +83,8 @@ def build_modules(force=False):
     for m in MODULES:
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
-        deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h")]
+        deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h"),
+                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h")]
         if force or not _newer(out, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                    "-DTORCH_EXTENSION_NAME=" + m, "-DTORCH_API_INCLUDE_EXTENSION_H",
@@ -82,7 +92,7 @@ def build_modules(force=False):
                    "-I/opt/rocm/include", "-I" + sysconfig.get_paths()["include"]]
             cmd += ["-I" + i for i in tinc]
             cmd += [src, "-o", out, "-L" + os.path.join(tdir, "lib"), "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu",
-                    "-ltorch_hip", "-ltorch_python", "-L" + LIBDIR, "-lflownet2_hip",
+                    "-ltorch_hip", "-ltorch_python", "-L" + LIBDIR, "-l" + MODULE_LIBS.get(m, "flownet2_hip"),
                     "-Wl,-rpath,$ORIGIN/lib", "-Wl,-rpath," + os.path.join(tdir, "lib")]
             jobs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         outs.append(out)
@@ -100,14 +110,14 @@ def main():
     ap.add_argument("--no-debug", action="store_true", help="skip libflownet2_hip_debug.so (profiling entry points)")
     ap.add_argument("--force", action="store_true")
     a = ap.parse_args()
-    if a.no_debug:
-        print(build_lib(a.force))
-    else:   # the two libraries share no object files: compile them side by side
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=2) as pool:
-            futs = [pool.submit(build_lib, a.force, False), pool.submit(build_lib, a.force, True)]
-            for f in futs:
-                print(f.result())
+    # the libraries share no object files: compile them side by side
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=3) as pool:
+        futs = [pool.submit(build_lib, a.force, False), pool.submit(build_lib, a.force, ext=True)]
+        if not a.no_debug:
+            futs.append(pool.submit(build_lib, a.force, True))
+        for f in futs:
+            print(f.result())
     if not a.lib:
         for o in build_modules(a.force):
             print(o)

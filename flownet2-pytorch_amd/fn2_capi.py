@@ -38,8 +38,14 @@ DEBUG_EXPORTS = ["fn2_debug_correlation_forward", "fn2_debug_correlation_backwar
 # correlation_forward / correlation_backward(..., algo=FN2_DEBUG_CORR_DENSE); FN2_EUNSUPPORTED outside their domain
 FN2_DEBUG_CORR_DENSE = 9000
 
+# libflownet2_hip_ext.so (include/flownet2_hip_ext.h): layers outside the drop-in boundary, a library and an ABI of their own
+EXT_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_ext.so")
+EXT_EXPORTS = ["fn2x_abi_version", "fn2x_correlation1d_output_shape", "fn2x_correlation1d_forward", "fn2x_correlation1d_backward"]
+FN2X_CORR1D_AUTO, FN2X_CORR1D_GENERAL, FN2X_CORR1D_TILED = 0, 1, 2
+
 _lib = None
 _dbg = None
+_ext = None
 
 
 def lib():
@@ -77,6 +83,20 @@ def debug_lib():
                 getattr(_dbg, name).restype = ctypes.c_int
         _dbg.fn2_debug_set_buffer.restype = None
     return _dbg
+
+
+def ext_lib():
+    """libflownet2_hip_ext.so: Correlation1d (csrc/correlation_1d.hip).  Self-contained; loads without libflownet2_hip.so."""
+    global _ext
+    if _ext is None:
+        import torch  # noqa: F401
+        if not os.path.exists(EXT_LIB_PATH):
+            raise RuntimeError(f"{EXT_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _ext = ctypes.CDLL(EXT_LIB_PATH)
+        for name in EXT_EXPORTS:
+            getattr(_ext, name).restype = ctypes.c_int
+    return _ext
 
 
 def check(rc, what):
@@ -117,6 +137,36 @@ def correlation_forward(in1, in2, pad, k, md, s1, s2, algo=FN2_CORR_AUTO, out=No
     with torch.cuda.device_of(in1):
         check(fn(_p(in1), _p(in2), _p(out), _dtype_code(in1), B, C, H, W, pad, k, md, s1, s2, algo, _stream(in1)), what)
     return out
+
+
+def correlation1d_output_shape(H, W, pad, md, s1, s2, sd=0):
+    n, oh, ow = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(ext_lib().fn2x_correlation1d_output_shape(H, W, pad, md, s1, s2, sd, ctypes.byref(n), ctypes.byref(oh), ctypes.byref(ow)),
+          "fn2x_correlation1d_output_shape")
+    return n.value, oh.value, ow.value
+
+
+def correlation1d_forward(in1, in2, pad, md, s1, s2, sd=0, algo=FN2X_CORR1D_AUTO, out=None):
+    """fn2x_correlation1d_forward on device tensors; ``algo``: FN2X_CORR1D_AUTO / _GENERAL / _TILED; ``out``: a preallocated result."""
+    import torch
+    B, C, H, W = in1.shape
+    nOut, oH, oW = correlation1d_output_shape(H, W, pad, md, s1, s2, sd)
+    if out is None:
+        out = torch.empty((B, nOut, oH, oW), dtype=in1.dtype, device=in1.device)
+    with torch.cuda.device_of(in1):
+        check(ext_lib().fn2x_correlation1d_forward(_p(in1), _p(in2), _p(out), _dtype_code(in1), B, C, H, W, pad, md, s1, s2, sd, algo,
+                                                   _stream(in1)), "fn2x_correlation1d_forward")
+    return out
+
+
+def correlation1d_backward(in1, in2, gout, pad, md, s1, s2, sd=0, algo=FN2X_CORR1D_AUTO, out=None):
+    import torch
+    B, C, H, W = in1.shape
+    g1, g2 = out if out is not None else (torch.empty_like(in1), torch.empty_like(in2))
+    with torch.cuda.device_of(in1):
+        check(ext_lib().fn2x_correlation1d_backward(_p(in1), _p(in2), _p(gout), _p(g1), _p(g2), _dtype_code(in1), B, C, H, W, pad, md,
+                                                    s1, s2, sd, algo, _stream(in1)), "fn2x_correlation1d_backward")
+    return g1, g2
 
 
 def correlation_forward_fused(in1, in2, buffer, channel_offset, negative_slope, pad, k, md, s1, s2, algo=FN2_CORR_AUTO):
