@@ -1,6 +1,7 @@
 """Builds libflownet2_hip.so (hand-written gfx950 HIP kernels + C ABI) and the three pybind
 modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without hipify; and libflownet2_hip_ext.so
-(include/flownet2_hip_ext.h: layers outside the drop-in boundary, Correlation1d) with its module correlation1d_cuda.
+(include/flownet2_hip_ext.h: layers outside the drop-in boundary, Correlation1d) with its module correlation1d_cuda; and
+libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h: CorrLookup, RAFT's correlation lookup) with its module corr_lookup_cuda.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -26,8 +27,12 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # libflownet2_hip_ext.so: a sibling library of its own (csrc/exports_ext.map), self-contained -- it does not link libflownet2_hip.so
 EXT_LIB = os.path.join(LIBDIR, "libflownet2_hip_ext.so")
 EXT_SRCS = ["capi_ext.hip", "correlation_1d.hip"]
-MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda"]
-MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext"}   # every other module links libflownet2_hip.so
+# sibling libraries by name: libflownet2_hip_<name>.so from its sources, csrc/exports_<name>.map and include/flownet2_hip_<name>.h;
+# the same flags, objects under lib/<name>/, and none links another
+SIBLINGS = {"ext": EXT_SRCS, "lookup": ["capi_lookup.hip", "corr_lookup.hip"]}
+MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda", "corr_lookup_cuda"]
+MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext", "corr_lookup_cuda": "flownet2_hip_lookup"}   # every other module links libflownet2_hip.so
+MAX_JOBS = 16
 
 
 def _newer(target, deps):
@@ -48,17 +53,19 @@ def _run(cmd):
 def build_lib(force=False, debug=False, ext=False):
     """libflownet2_hip.so (the product: public C ABI only) or, with debug=True, libflownet2_hip_debug.so: the same kernels plus
     the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs);
-    with ext=True libflownet2_hip_ext.so (EXT_SRCS, the same flags, its own version script)."""
-    objdir = os.path.join(LIBDIR, "ext") if ext else os.path.join(LIBDIR, "debug") if debug else LIBDIR
-    lib = EXT_LIB if ext else os.path.join(LIBDIR, "libflownet2_hip_debug.so") if debug else LIB
-    vmap = os.path.join(CSRC, "exports_ext.map" if ext else "exports.map")
+    with ext=NAME the sibling library libflownet2_hip_NAME.so (SIBLINGS[NAME], the same flags, its own version script);
+    ext=True means "ext"."""
+    ext = "ext" if ext is True else ext
+    objdir = os.path.join(LIBDIR, ext) if ext else os.path.join(LIBDIR, "debug") if debug else LIBDIR
+    lib = os.path.join(LIBDIR, "libflownet2_hip_%s.so" % ext) if ext else os.path.join(LIBDIR, "libflownet2_hip_debug.so") if debug else LIB
+    vmap = os.path.join(CSRC, "exports_%s.map" % ext if ext else "exports.map")
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip.h"))
     if ext:
-        hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"))
+        hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip_%s.h" % ext))
     objs, jobs = [], []
-    for src in (EXT_SRCS if ext else KERNEL_SRCS):
+    for src in (SIBLINGS[ext] if ext else KERNEL_SRCS):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         if force or not _newer(o, [s] + hdrs):
@@ -66,7 +73,7 @@ def build_lib(force=False, debug=False, ext=False):
         objs.append(o)
     if jobs:   # the translation units are independent: compile them side by side (each hipcc is single-threaded)
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1, MAX_JOBS)) as pool:
             list(pool.map(_run, jobs))
     if force or not _newer(lib, objs + [vmap]):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + vmap, "-o", lib] + objs)
@@ -84,7 +91,7 @@ def build_modules(force=False):
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
         deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h")]
+                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"), os.path.join(HERE, "..", "include", "flownet2_hip_lookup.h")]
         if force or not _newer(out, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                    "-DTORCH_EXTENSION_NAME=" + m, "-DTORCH_API_INCLUDE_EXTENSION_H",
@@ -112,8 +119,8 @@ def main():
     a = ap.parse_args()
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=3) as pool:
-        futs = [pool.submit(build_lib, a.force, False), pool.submit(build_lib, a.force, ext=True)]
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        futs = [pool.submit(build_lib, a.force, False)] + [pool.submit(build_lib, a.force, ext=name) for name in SIBLINGS]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))
         for f in futs:

@@ -43,9 +43,15 @@ EXT_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_ext.so")
 EXT_EXPORTS = ["fn2x_abi_version", "fn2x_correlation1d_output_shape", "fn2x_correlation1d_forward", "fn2x_correlation1d_backward"]
 FN2X_CORR1D_AUTO, FN2X_CORR1D_GENERAL, FN2X_CORR1D_TILED = 0, 1, 2
 
+# libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h): CorrLookup, RAFT's correlation lookup; the third library
+LOOKUP_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_lookup.so")
+LOOKUP_EXPORTS = ["fn2l_abi_version", "fn2l_corr_lookup_forward", "fn2l_corr_lookup_backward"]
+FN2L_LOOKUP_AUTO, FN2L_LOOKUP_GENERAL, FN2L_LOOKUP_STAGED = 0, 1, 2
+
 _lib = None
 _dbg = None
 _ext = None
+_lookup = None
 
 
 def lib():
@@ -97,6 +103,20 @@ def ext_lib():
         for name in EXT_EXPORTS:
             getattr(_ext, name).restype = ctypes.c_int
     return _ext
+
+
+def lookup_lib():
+    """libflownet2_hip_lookup.so: CorrLookup (csrc/corr_lookup.hip).  Self-contained; loads without the other two libraries."""
+    global _lookup
+    if _lookup is None:
+        import torch  # noqa: F401
+        if not os.path.exists(LOOKUP_LIB_PATH):
+            raise RuntimeError(f"{LOOKUP_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _lookup = ctypes.CDLL(LOOKUP_LIB_PATH)
+        for name in LOOKUP_EXPORTS:
+            getattr(_lookup, name).restype = ctypes.c_int
+    return _lookup
 
 
 def check(rc, what):
@@ -166,6 +186,35 @@ def correlation1d_backward(in1, in2, gout, pad, md, s1, s2, sd=0, algo=FN2X_CORR
     with torch.cuda.device_of(in1):
         check(ext_lib().fn2x_correlation1d_backward(_p(in1), _p(in2), _p(gout), _p(g1), _p(g2), _dtype_code(in1), B, C, H, W, pad, md,
                                                     s1, s2, sd, algo, _stream(in1)), "fn2x_correlation1d_backward")
+    return g1, g2
+
+
+def corr_lookup_forward(fmap1, fmap2, coords, radius, scale, algo=FN2L_LOOKUP_AUTO, out=None):
+    """fn2l_corr_lookup_forward on contiguous device tensors; ``algo``: FN2L_LOOKUP_AUTO / _GENERAL / _STAGED; ``out``: a
+    preallocated B x (2 radius + 1)^2 x H x W result."""
+    import torch
+    B, C, H, W = fmap1.shape
+    H2, W2 = fmap2.shape[2:]
+    assert fmap1.is_contiguous() and fmap2.is_contiguous() and coords.is_contiguous() and tuple(coords.shape) == (B, 2, H, W)
+    if out is None:
+        out = torch.empty((B, (2 * radius + 1) ** 2, H, W), dtype=fmap1.dtype, device=fmap1.device)
+    with torch.cuda.device_of(fmap1):
+        check(lookup_lib().fn2l_corr_lookup_forward(_p(fmap1), _p(fmap2), _p(coords), _p(out), _dtype_code(fmap1), B, C, H, W, H2, W2,
+                                                    radius, ctypes.c_float(scale), algo, _stream(fmap1)), "fn2l_corr_lookup_forward")
+    return out
+
+
+def corr_lookup_backward(fmap1, fmap2, coords, gout, radius, scale, algo=FN2L_LOOKUP_AUTO, out=None):
+    """fn2l_corr_lookup_backward: (grad_fmap1, grad_fmap2); ``out``: the two preallocated gradients (no pre-zeroing needed)."""
+    import torch
+    B, C, H, W = fmap1.shape
+    H2, W2 = fmap2.shape[2:]
+    assert fmap1.is_contiguous() and fmap2.is_contiguous() and coords.is_contiguous() and gout.is_contiguous()
+    g1, g2 = out if out is not None else (torch.empty_like(fmap1), torch.empty_like(fmap2))
+    with torch.cuda.device_of(fmap1):
+        check(lookup_lib().fn2l_corr_lookup_backward(_p(fmap1), _p(fmap2), _p(coords), _p(gout), _p(g1), _p(g2), _dtype_code(fmap1), B, C,
+                                                     H, W, H2, W2, radius, ctypes.c_float(scale), algo, _stream(fmap1)),
+              "fn2l_corr_lookup_backward")
     return g1, g2
 
 
