@@ -6,8 +6,8 @@
 // t runs over -dr .. dr (single_direction 0), -dr .. 0 (-1) or 0 .. dr (+1), dr = md / s2; a term whose operand column or output
 // column lies outside is absent, not a zero factor.  Padding is horizontal only; there is no kernel_size (it is 1).
 //
-// The arithmetic is the general 2-D kernel's (correlation_direct.hip) for k = 1, literally, so that for pad == md the result is
-// the centre row of the 2-D layer's displacement window bit for bit:
+// The arithmetic is the general 2-D kernel's (correlation_direct.hip) for k = 1, literally (corr_arith.h holds the channel sum both
+// call), so that for pad == md the result is the centre row of the 2-D layer's displacement window bit for bit:
 //   forward : four partial sums over the channels c = 0,1,2,3 (mod 4) in ascending order, the C % 4 leftover channels appended
 //             to the first; 0 + ((s0 + s1) + (s2 + s3)); / C; one rounding to T; one product = fwd_prod<T> (corr_arith.h)
 //   backward: one sequential sum over ascending t of (0 + gO) * v, starting at +0; / C; one rounding
@@ -17,8 +17,9 @@
 // General kernels (corr1d_*_general): one lane per output element / input element, any parameters, all four types.
 //
 // Tiled kernels (corr1d_*_tiled): s1 = s2 = 1, pad == md, 1 <= nOut <= 81, float / half / bf16; every element has the general
-// kernel's bits (NaN where it has NaN).  The tiling is correlation_dense.hip's with the row displacement removed: the four
-// channels of one pixel side by side in LDS, the next four channels in flight from global memory (two buffers, one barrier per step).
+// kernel's bits (NaN where it has NaN).  The tiling is correlation_dense.hip's with the row displacement removed, and what the
+// two have in common is one piece of code, corr_tiled.h: the four channels of one pixel side by side in LDS, the next four channels
+// in flight from global memory (two buffers, one barrier per step), the forward's step, the backward's product loop.
 //   forward : tile 32 x 4 pixels; one wave per group of nine displacements (NG waves, NG in {1,2,3,5,7,9}: the smallest that
 //             covers nOut; displacements from nOut on are computed on zeros and not stored); one lane = 2 adjacent pixels x 9
 //             displacements x 4 chains.  The in2 image is 4 rows of 32 + 9 NG - 1 columns that start at column tx0 + tmin: the
@@ -33,7 +34,7 @@
 #include <type_traits>
 
 #include "corr1d.h"
-#include "corr_arith.h"
+#include "corr_tiled.h"
 
 namespace fn2 {
 
@@ -83,16 +84,7 @@ __global__ __launch_bounds__(256) void corr1d_fwd_general(const T *__restrict__ 
         if (x1 >= 0 && x1 < p.W && x2 >= 0 && x2 < p.W) {   // otherwise the term is absent
             const T *pa = in1 + (long)n * p.C * HW + (long)y1 * p.W + x1;
             const T *pb = in2 + (long)n * p.C * HW + (long)y1 * p.W + x2;
-            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-            int c = 0;
-            for (; c + 4 <= p.C; c += 4) {
-                s0 += fwd_prod<T>(pa[(long)(c + 0) * HW], pb[(long)(c + 0) * HW]);
-                s1 += fwd_prod<T>(pa[(long)(c + 1) * HW], pb[(long)(c + 1) * HW]);
-                s2 += fwd_prod<T>(pa[(long)(c + 2) * HW], pb[(long)(c + 2) * HW]);
-                s3 += fwd_prod<T>(pa[(long)(c + 3) * HW], pb[(long)(c + 3) * HW]);
-            }
-            for (; c < p.C; ++c) s0 += fwd_prod<T>(pa[(long)c * HW], pb[(long)c * HW]);
-            acc += (s0 + s1) + (s2 + s3);
+            acc += fwd_channel_sum<T>(pa, pb, p.C, HW);   // four chains over the channels (corr_arith.h)
         }
         const int nelems = p.C;
         const float res = acc / nelems;
@@ -144,14 +136,6 @@ __global__ __launch_bounds__(256) void corr1d_bwd_general(const T *__restrict__ 
     }
 }
 
-inline unsigned stream_grid(long nthreads, long cap_blocks)
-{
-    long blocks = (nthreads + 255) / 256;
-    if (blocks > cap_blocks) blocks = cap_blocks;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 template <typename T>
 int fwd_general_launch(const void *in1, const void *in2, void *out, const Corr1dP &p, hipStream_t s)
 {
@@ -173,40 +157,10 @@ int bwd_general_launch(const void *in1, const void *in2, const void *gout, void 
 }
 
 // ================================================================ tiled kernels
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int TILED_MAX_NOUT = 81;
 constexpr int GD = 9;              // forward: displacements per wave
-constexpr int FTW = 32, FTH = 4;   // forward tile (pixels)
-constexpr int BTW = 32, BTH = 8;   // backward tile
-constexpr int BG = 3;              // backward: displacements per scheduling group
 // waves per SIMD the backward is built for: 81 gO factors alone are 82 registers
 constexpr int bwd_waves(int nb) { return nb > 45 ? 3 : 4; }
-
-// element type of the forward's LDS image: bf16 is widened (its products are formed in fp32), half is multiplied in half
-template <typename T> struct Lds { typedef float type; };
-template <> struct Lds<half_t> { typedef half_t type; };
-
-template <typename T> __device__ __forceinline__ void store_pair(T *p, T v0, T v1)
-{
-    if constexpr (sizeof(T) == 4) {
-        store_out(reinterpret_cast<f2 *>(p), (f2){v0, v1});
-    } else {
-        typedef T t2 __attribute__((ext_vector_type(2)));
-        store_out(reinterpret_cast<unsigned *>(p), __builtin_bit_cast(unsigned, (t2){v0, v1}));
-    }
-}
-
-// (w[hi], w[hi]) * v as one packed multiply (correlation_dense.hip: a broadcast factor costs no register pair of its own); the add
-// is a separate instruction: two roundings per mul + add as everywhere
-__device__ __forceinline__ f2 pk_mul_bcast(bool hi, f2 w, f2 v)   // hi: a constant once the caller's loop is unrolled
-{
-    f2 r;
-    if (hi) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(w), "v"(v));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(w), "v"(v));
-    return r;
-}
 
 // ---------------------------------------------------------------- forward
 template <typename T, int NG>
@@ -232,8 +186,8 @@ __global__ __launch_bounds__(NG * 64) void corr1d_fwd_tiled(const T *__restrict_
     const int need = FTW + p.nOut - 1;   // in2 columns of the image that a stored displacement reads
 
     // what this lane stages of every quad: pixel e of the in1 tile or (e - N1) of the in2 tile; -1 = zero (outside the image)
-    const T *src[NLD];
-    int goff[NLD], lidx[NLD];
+    QuadStage<T, L, NLD, NT> st;
+    st.C = p.C; st.HW = HW;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         const int e = tid + i * NT;
@@ -242,32 +196,19 @@ __global__ __launch_bounds__(NG * 64) void corr1d_fwd_tiled(const T *__restrict_
         if (e < N1) {
             row = e / FTW; col = e % FTW;
             x = tx0 + col;
-            src[i] = a; lidx[i] = row * P1 + col;
+            st.src[i] = a; st.lidx[i] = row * P1 + col;
         } else {
             const int e2 = e - N1;
             row = e2 / C2; col = e2 % C2;
             x = tx0 + p.tmin + col;
-            src[i] = b; lidx[i] = SA + row * P2 + col;
+            st.src[i] = b; st.lidx[i] = SA + row * P2 + col;
             ok = ok && col < need;
         }
         const int y = ty0 + row;
         ok = ok && y < p.H && x >= 0 && x < p.W;
-        goff[i] = ok ? y * p.W + x : -1;
-        if (e >= NPOS) lidx[i] = -1;
+        st.goff[i] = ok ? y * p.W + x : -1;
+        if (e >= NPOS) st.lidx[i] = -1;
     }
-
-    l4 val[NLD];
-    auto gload = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;   // always a load from inside the tensor (no branch around it), then the select
-                const L v = (L)src[i][max(goff[i], 0) + min(c, p.C - 1) * HW];
-                val[i][k] = (goff[i] >= 0 && c < p.C) ? v : (L)0.0f;
-            }
-        }
-    };
 
     f4 acc[2][GD];   // component = chain (channel mod 4)
 #pragma unroll
@@ -277,46 +218,11 @@ __global__ __launch_bounds__(NG * 64) void corr1d_fwd_tiled(const T *__restrict_
 
     const int nq = (p.C + 3) / 4, full = p.C / 4, rem = p.C & 3;
     const int offA = r * P1 + 2 * xg, offB = SA + r * P2 + 2 * xg + GD * grp;
-    gload(0);
+    st.load(0);
     for (int q = 0; q < nq; ++q) {
         l4 *buf = sm[q & 1];
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            if (lidx[i] >= 0) buf[lidx[i]] = val[i];
-        __syncthreads();   // the only barrier of a step: the buffer written next was last read before this one
-        if (q + 1 < nq) gload(q + 1);
-        const l4 a0 = buf[offA], a1 = buf[offA + 1];
-        l4 bv[GD + 1];
-#pragma unroll
-        for (int j = 0; j < GD + 1; ++j) bv[j] = buf[offB + j];
-        if (q < full) {
-#pragma unroll
-            for (int d = 0; d < GD; ++d) {
-#pragma unroll
-                for (int px = 0; px < 2; ++px) {
-                    const l4 av = px ? a1 : a0;
-                    const l4 w = bv[d + px];
-                    f4 pr;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) pr[k] = fwd_prod<L>(av[k], w[k]);
-                    acc[px][d] += pr;
-                }
-            }
-        } else {   // the C % 4 leftover channels go to the first chain, in order
-#pragma unroll
-            for (int d = 0; d < GD; ++d) {
-#pragma unroll
-                for (int px = 0; px < 2; ++px) {
-                    const l4 av = px ? a1 : a0;
-                    const l4 w = bv[d + px];
-                    float s0 = acc[px][d][0];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        if (k < rem) s0 += fwd_prod<L>(av[k], w[k]);
-                    acc[px][d][0] = s0;
-                }
-            }
-        }
+        st.step(buf, q, nq);
+        fwd_quad<L, GD>(acc, buf, offA, offB, q < full, rem);
     }
 
     const int y = ty0 + r, x0 = tx0 + 2 * xg;
@@ -330,21 +236,12 @@ __global__ __launch_bounds__(NG * 64) void corr1d_fwd_tiled(const T *__restrict_
         T res2[2];
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-            const f4 s = acc[px][d];
-            float sum = 0.0f;
-            sum += (s[0] + s[1]) + (s[2] + s[3]);
             const int x2 = x0 + px + p.tmin + o;
-            if (!(x2 >= 0 && x2 < p.W)) sum = 0.0f;   // absent, not zero-multiplied
+            const float sum = fwd_lane_sum(acc[px][d], x2 >= 0 && x2 < p.W);
             const float res = sum / nelems;
             res2[px] = (T)res;
         }
-        T *od = out + (long)n * obs + ((long)o * p.H + y) * p.W + x0;
-        if (vec) {
-            store_pair<T>(od, res2[0], res2[1]);
-        } else {
-            store_out(od, res2[0]);
-            if (x0 + 1 < p.W) store_out(od + 1, res2[1]);
-        }
+        store_results<T>(out + (long)n * obs + ((long)o * p.H + y) * p.W + x0, res2, vec, x0 + 1 < p.W);
     }
 }
 
@@ -378,32 +275,23 @@ void corr1d_bwd_tiled(const T *__restrict__ in1, const T *__restrict__ in2, cons
     const int y = ty0 + yl, x = tx0 + xl;
     const bool inimg = y < p.H && x < p.W;
 
-    int goff[NLD];
+    QuadStage<T, float, NLD, NT> st;   // BTH rows of `inp`, columns as above
+    st.C = p.C; st.HW = HW;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         const int e = tid + i * NT;
         const int row = e / CC, ci = e % CC;
         const int yy = ty0 + row, xx = which ? tx0 + BTW - 1 - p.tmin - ci : tx0 + p.tmin + ci;
         const bool ok = e < NPOS && ci < need && yy < p.H && xx >= 0 && xx < p.W;
-        goff[i] = ok ? yy * p.W + xx : -1;
+        st.src[i] = inp;
+        st.goff[i] = ok ? yy * p.W + xx : -1;
+        st.lidx[i] = e < NPOS ? e : -1;
     }
-    f4 val[NLD];
-    auto gload = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;   // always a load from inside the tensor (no branch around it), then the select
-                const float v = (float)inp[max(goff[i], 0) + min(c, p.C - 1) * HW];
-                val[i][k] = (goff[i] >= 0 && c < p.C) ? v : 0.0f;
-            }
-        }
-    };
-    gload(qbeg);
+    st.load(qbeg);
 
     // the gO factors of this pixel, once for all channels; 0 where the term is absent
     const int sgn = which ? -1 : 1;
-    f2 wp[(NB + 1) / 2];   // factor o is half o & 1 of pair o / 2
+    f2 wp[(NB + 1) / 2];   // factor o is half o & 1 of pair o / 2 (bwd_quad)
 #pragma unroll
     for (int o = 0; o < NB; ++o) {
         const int ox = x + sgn * (p.tmin + o);   // the other operand's column
@@ -419,70 +307,19 @@ void corr1d_bwd_tiled(const T *__restrict__ in1, const T *__restrict__ in2, cons
     const int centre = yl * CC + (which ? BTW - 1 - xl : xl);
     for (int q = qbeg; q < qend; ++q) {
         f4 *buf = sm[(q - qbeg) & 1];
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int e = tid + i * NT;
-            if (e < NPOS) buf[e] = val[i];
-        }
-        __syncthreads();   // the only barrier of a step: the buffer written next was last read before this one
-        if (q + 1 < qend) gload(q + 1);
-        const f4 *ctr = buf + centre;
-        f2 s01 = (f2){0.0f, 0.0f}, s23 = (f2){0.0f, 0.0f};
-        // BG displacements at a time, the reads of the next group in flight (correlation_dense.hip); a group from nOut on is
-        // skipped as a whole, a displacement from nOut on inside the last group by itself: both wave-uniform
-        f4 cur[BG], nxt[BG];
-#pragma unroll
-        for (int i = 0; i < BG; ++i) cur[i] = ctr[i];
-#pragma unroll
-        for (int t0 = 0; t0 < NB; t0 += BG) {
-            if (t0 < nOut) {
-#pragma unroll
-                for (int i = 0; i < BG; ++i) {
-                    const int tn = t0 + BG + i;
-                    if (tn < NB) nxt[i] = ctr[tn];
-                }
-#pragma unroll
-                for (int i = 0; i < BG; ++i) {
-                    const int o = t0 + i;
-                    if (o < NB && o < nOut) {
-                        s01 += pk_mul_bcast(o & 1, wp[o / 2], cur[i].xy);
-                        s23 += pk_mul_bcast(o & 1, wp[o / 2], cur[i].zw);
-                    }
-                }
-                // the sums are used under `if (inimg)` only: without this anchor the adds are sunk there, behind all the products
-                asm volatile("" : "+v"(s01), "+v"(s23));
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < BG; ++i) cur[i] = nxt[i];
-            }
-        }
-        const f4 sum = (f4){s01.x, s01.y, s23.x, s23.y};
-        if (inimg) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;
-                if (c < p.C) store_out(g + c * HW + y * p.W + x, (T)(sum[k] / nelems));
-            }
-        }
+        st.step(buf, q, qend);
+        // a group of displacements from nOut on is skipped as a whole, a displacement from nOut on inside the last group by itself:
+        // both wave-uniform
+        const f4 sum = bwd_quad<NB>(buf + centre, wp, nOut, [](int t) { return t; });
+        if (inimg) bwd_store_quad(g, y * p.W + x, q, p.C, HW, sum, nelems);
     }
-}
-
-// one batch item is indexed with ints, the grid's y / z extents are 16-bit
-bool tiled_fits(const Corr1dP &p)
-{
-    const long HW = (long)p.H * p.W;
-    if (((long)p.C + 4) * HW >= (1L << 31) || (long)p.nOut * HW >= (1L << 31)) return false;   // C + 4: the zero-filled tail of the last quad
-    if (p.B > 32767) return false;
-    const long tiles = (long)((p.W + FTW - 1) / FTW) * ((p.H + FTH - 1) / FTH);
-    return tiles < (1L << 31);
 }
 
 template <typename T, int NG>
 int fwd_tiled_launch(const void *in1, const void *in2, void *out, const Corr1dP &p, hipStream_t s)
 {
     const int tilesX = (p.W + FTW - 1) / FTW, tilesY = (p.H + FTH - 1) / FTH;
-    // two results of a lane go out as one store where every row of every plane keeps the pair aligned
-    const int vec = (p.W % 2 == 0) && aligned(out, 2 * sizeof(T));
+    const int vec = fwd_pairs_aligned(p.W, (long)p.nOut * p.H * p.W, out, sizeof(T));
     hipLaunchKernelGGL((corr1d_fwd_tiled<T, NG>), dim3(tilesX * tilesY, 1, p.B), dim3(NG * 64), 0, s, static_cast<const T *>(in1),
                        static_cast<const T *>(in2), static_cast<T *>(out), p, tilesX, vec);
     return launch_status();
@@ -493,13 +330,8 @@ int bwd_tiled_launch(const void *in1, const void *in2, const void *gout, void *g
 {
     const int tilesX = (p.W + BTW - 1) / BTW, tilesY = (p.H + BTH - 1) / BTH;
     const int nq = (p.C + 3) / 4;
-    // split the channels until about four workgroups per CU are in the grid (small maps, many channels)
-    const long base = (long)tilesX * tilesY * p.B * 2;
-    int split = (int)((1024 + base - 1) / base);
-    if (split > nq) split = nq;
-    if (split < 1) split = 1;
-    const int qper = (nq + split - 1) / split;
-    split = (nq + qper - 1) / qper;
+    int split;
+    const int qper = bwd_channel_split((long)tilesX * tilesY * p.B * 2, nq, &split);
     hipLaunchKernelGGL((corr1d_bwd_tiled<T, NB>), dim3(tilesX * tilesY, split, p.B * 2), dim3(BTW * BTH), 0, s,
                        static_cast<const T *>(in1), static_cast<const T *>(in2), static_cast<const T *>(gout), static_cast<T *>(g1),
                        static_cast<T *>(g2), p, tilesX, qper);

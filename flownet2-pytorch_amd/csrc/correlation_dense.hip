@@ -15,11 +15,8 @@
 //   every sum a chain that starts at +0 can hold.
 // mul and add stay two roundings (-ffp-contract=off); packed and scalar fp32 / f16 instructions round alike.
 //
-// Design.  A workgroup owns one batch item and a tile of pixels and walks the channels four at a time.  The four channels of one
-// pixel are staged side by side (16 bytes for fp32 / bf16-as-fp32, 8 bytes for half), so every LDS read is one aligned
-// ds_read_b128 / b64 whatever the displacement, and the four lanes of the vector are the forward's four chains.  The next four
-// channels travel from global memory into registers while the current ones are multiplied (two LDS buffers, one barrier per
-// step).
+// Design.  The channel-quad tiling of corr_tiled.h (shared with correlation_1d.hip): the staging pipeline, the forward's step and
+// lane sum, the backward's product loop and the launch arithmetic live there; here is what the 2-D search makes its own.
 //   forward : tile 32 x 4 pixels, one wave per dy row (2md+1 waves), one lane = 2 adjacent pixels x (2md+1) dx x 4 chains
 //             (72 accumulators at md = 4); per 4 channels a lane reads 2 + 2md+2 vectors for 8(2md+1) products.
 //             LDS pitches are odd (33, 32+2md+1 vectors): the lanes of one row use the even 16-byte slots, those of the next row
@@ -30,47 +27,16 @@
 //             are split over blockIdx.y where the tiles alone do not fill the chip.
 #include <type_traits>
 
-#include "corr_arith.h"
 #include "corr_params.h"
+#include "corr_tiled.h"
 
 namespace fn2 {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int DENSE_MAX_MD = 4;
-constexpr int FTW = 32, FTH = 4;   // forward tile (pixels)
-constexpr int BTW = 32, BTH = 8;   // backward tile
-constexpr int BG = 3;              // backward: displacements per scheduling group
 // waves per SIMD the backward is built for: the (2md+1)^2 gO factors alone are 82 registers at md = 4
 constexpr int bwd_waves(int md) { return md >= 4 ? 3 : 4; }
-
-// element type of the forward's LDS image: bf16 is widened (its products are formed in fp32), half is multiplied in half
-template <typename T> struct Lds { typedef float type; };
-template <> struct Lds<half_t> { typedef half_t type; };
-
-template <typename T> __device__ __forceinline__ void store_pair(T *p, T v0, T v1)
-{
-    if constexpr (sizeof(T) == 4) {
-        store_out(reinterpret_cast<f2 *>(p), (f2){v0, v1});
-    } else {
-        typedef T t2 __attribute__((ext_vector_type(2)));
-        store_out(reinterpret_cast<unsigned *>(p), __builtin_bit_cast(unsigned, (t2){v0, v1}));
-    }
-}
-
-// (w[hi], w[hi]) * v as one packed multiply: op_sel picks the half of the pair `w` for both results, so a broadcast factor costs
-// no register pair of its own (the compiler's own v_pk_mul_f32 keeps (w, w) for every displacement and spills).  Two roundings
-// per mul + add as everywhere: the add is a separate instruction.
-__device__ __forceinline__ f2 pk_mul_bcast(bool hi, f2 w, f2 v)   // hi: a constant once the caller's loop is unrolled
-{
-    f2 r;
-    if (hi) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(w), "v"(v));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(w), "v"(v));
-    return r;
-}
 
 // ---------------------------------------------------------------- forward
 template <typename T, int MD>
@@ -95,8 +61,8 @@ __global__ __launch_bounds__((2 * MD + 1) * 64) void corr_fwd_dense(const T *__r
     const T *b = in2 + (long)n * p.C * HW;
 
     // what this lane stages of every quad: pixel e of the in1 tile or (e - N1) of the in2 tile; -1 = outside the image (zero)
-    const T *src[NLD];
-    int goff[NLD], lidx[NLD];
+    QuadStage<T, L, NLD, NT> st;
+    st.C = p.C; st.HW = HW;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         const int e = tid + i * NT;
@@ -104,30 +70,17 @@ __global__ __launch_bounds__((2 * MD + 1) * 64) void corr_fwd_dense(const T *__r
         if (e < N1) {
             row = e / FTW; col = e % FTW;
             y = ty0 + row; x = tx0 + col;
-            src[i] = a; lidx[i] = row * P1 + col;
+            st.src[i] = a; st.lidx[i] = row * P1 + col;
         } else {
             const int e2 = e - N1;
             row = e2 / C2; col = e2 % C2;
             y = ty0 - MD + row; x = tx0 - MD + col;
-            src[i] = b; lidx[i] = SA + row * P2 + col;
+            st.src[i] = b; st.lidx[i] = SA + row * P2 + col;
         }
         const bool ok = e < NPOS && y >= 0 && y < p.H && x >= 0 && x < p.W;
-        goff[i] = ok ? y * p.W + x : -1;
-        if (e >= NPOS) lidx[i] = -1;
+        st.goff[i] = ok ? y * p.W + x : -1;
+        if (e >= NPOS) st.lidx[i] = -1;
     }
-
-    l4 val[NLD];
-    auto gload = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;   // always a load from inside the tensor (no branch around it), then the select
-                const L v = (L)src[i][max(goff[i], 0) + min(c, p.C - 1) * HW];
-                val[i][k] = (goff[i] >= 0 && c < p.C) ? v : (L)0.0f;
-            }
-        }
-    };
 
     f4 acc[2][D];   // component = chain (channel mod 4)
 #pragma unroll
@@ -137,46 +90,11 @@ __global__ __launch_bounds__((2 * MD + 1) * 64) void corr_fwd_dense(const T *__r
 
     const int nq = (p.C + 3) / 4, full = p.C / 4, rem = p.C & 3;
     const int offA = r * P1 + 2 * xg, offB = SA + (r + dyI) * P2 + 2 * xg;
-    gload(0);
+    st.load(0);
     for (int q = 0; q < nq; ++q) {
         l4 *buf = sm[q & 1];
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            if (lidx[i] >= 0) buf[lidx[i]] = val[i];
-        __syncthreads();   // the only barrier of a step: the buffer written next was last read before this one
-        if (q + 1 < nq) gload(q + 1);
-        const l4 a0 = buf[offA], a1 = buf[offA + 1];
-        l4 bv[D + 1];
-#pragma unroll
-        for (int j = 0; j < D + 1; ++j) bv[j] = buf[offB + j];
-        if (q < full) {
-#pragma unroll
-            for (int dx = 0; dx < D; ++dx) {
-#pragma unroll
-                for (int px = 0; px < 2; ++px) {
-                    const l4 av = px ? a1 : a0;
-                    const l4 w = bv[dx + px];
-                    f4 pr;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) pr[k] = fwd_prod<L>(av[k], w[k]);
-                    acc[px][dx] += pr;
-                }
-            }
-        } else {   // the C % 4 leftover channels go to the first chain, in order
-#pragma unroll
-            for (int dx = 0; dx < D; ++dx) {
-#pragma unroll
-                for (int px = 0; px < 2; ++px) {
-                    const l4 av = px ? a1 : a0;
-                    const l4 w = bv[dx + px];
-                    float s0 = acc[px][dx][0];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        if (k < rem) s0 += fwd_prod<L>(av[k], w[k]);
-                    acc[px][dx][0] = s0;
-                }
-            }
-        }
+        st.step(buf, q, nq);
+        fwd_quad<L, D>(acc, buf, offA, offB, q < full, rem);
     }
 
     const int y = ty0 + r, x0 = tx0 + 2 * xg;
@@ -190,22 +108,13 @@ __global__ __launch_bounds__((2 * MD + 1) * 64) void corr_fwd_dense(const T *__r
         T res2[2];
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-            const f4 s = acc[px][dx];
-            float sum = 0.0f;
-            sum += (s[0] + s[1]) + (s[2] + s[3]);
             const int x2 = x0 + px + dx - MD;
-            if (!(yok && x2 >= 0 && x2 < p.W)) sum = 0.0f;   // absent, not zero-multiplied
+            const float sum = fwd_lane_sum(acc[px][dx], yok && x2 >= 0 && x2 < p.W);
             float res = sum / nelems;
             if (p.slope != 1.0f) res = res > 0.0f ? res : (float)(T)res * p.slope;
             res2[px] = (T)res;
         }
-        T *od = o + (long)dx * HW;
-        if (vec) {
-            store_pair<T>(od, res2[0], res2[1]);
-        } else {
-            store_out(od, res2[0]);
-            if (x0 + 1 < p.W) store_out(od + 1, res2[1]);
-        }
+        store_results<T>(o + (long)dx * HW, res2, vec, x0 + 1 < p.W);
     }
 }
 
@@ -237,32 +146,23 @@ void corr_bwd_dense(const T *__restrict__ in1, const T *__restrict__ in2, const 
     const int y = ty0 + yl, x = tx0 + xl;
     const bool inimg = y < p.H && x < p.W;
 
-    int goff[NLD];
+    QuadStage<T, float, NLD, NT> st;   // the tile + halo of `inp`; for gradInput2 written point-mirrored
+    st.C = p.C; st.HW = HW;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         const int e = tid + i * NT;
         const int row = e / CC, col = e % CC;
         const int yy = ty0 - MD + row, xx = tx0 - MD + col;
         const bool ok = e < NPOS && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        goff[i] = ok ? yy * p.W + xx : -1;
+        st.src[i] = inp;
+        st.goff[i] = ok ? yy * p.W + xx : -1;
+        st.lidx[i] = e < NPOS ? (which ? NPOS - 1 - e : e) : -1;
     }
-    f4 val[NLD];
-    auto gload = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;   // always a load from inside the tensor (no branch around it), then the select
-                const float v = (float)inp[max(goff[i], 0) + min(c, p.C - 1) * HW];
-                val[i][k] = (goff[i] >= 0 && c < p.C) ? v : 0.0f;
-            }
-        }
-    };
-    gload(qbeg);
+    st.load(qbeg);
 
     // the gO factors of this pixel, once for all channels; 0 where the term is absent
     const int sgn = which ? -1 : 1;
-    f2 wp[(D * D + 1) / 2];   // factor tc is half tc & 1 of pair tc / 2
+    f2 wp[(D * D + 1) / 2];   // factor tc is half tc & 1 of pair tc / 2 (bwd_quad)
 #pragma unroll
     for (int tc = 0; tc < D * D; ++tc) {
         const int dy = tc / D - MD, dx = tc % D - MD;
@@ -280,68 +180,17 @@ void corr_bwd_dense(const T *__restrict__ in1, const T *__restrict__ in2, const 
     const int centre = which ? NPOS - 1 - c0 : c0;
     for (int q = qbeg; q < qend; ++q) {
         f4 *buf = sm[(q - qbeg) & 1];
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int e = tid + i * NT;
-            if (e < NPOS) buf[which ? NPOS - 1 - e : e] = val[i];
-        }
-        __syncthreads();   // the only barrier of a step: the buffer written next was last read before this one
-        if (q + 1 < qend) gload(q + 1);
-        const f4 *ctr = buf + centre;
-        f2 s01 = (f2){0.0f, 0.0f}, s23 = (f2){0.0f, 0.0f};
-        // BG displacements at a time, the reads of the next group in flight: left alone, the scheduler forms every product first
-        // (they are independent, the two sums are chains) and spills them
-        f4 cur[BG], nxt[BG];
-#pragma unroll
-        for (int i = 0; i < BG; ++i) cur[i] = ctr[((i / D) - MD) * CC + (i % D) - MD];
-#pragma unroll
-        for (int t0 = 0; t0 < D * D; t0 += BG) {
-#pragma unroll
-            for (int i = 0; i < BG; ++i) {
-                const int tn = t0 + BG + i;
-                if (tn < D * D) nxt[i] = ctr[((tn / D) - MD) * CC + (tn % D) - MD];
-            }
-#pragma unroll
-            for (int i = 0; i < BG; ++i) {
-                const int tc = t0 + i;
-                if (tc < D * D) {
-                    s01 += pk_mul_bcast(tc & 1, wp[tc / 2], cur[i].xy);
-                    s23 += pk_mul_bcast(tc & 1, wp[tc / 2], cur[i].zw);
-                }
-            }
-            // the sums are used under `if (inimg)` only: without this anchor the adds are sunk there, behind all the products
-            asm volatile("" : "+v"(s01), "+v"(s23));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < BG; ++i) cur[i] = nxt[i];
-        }
-        const f4 sum = (f4){s01.x, s01.y, s23.x, s23.y};
-        if (inimg) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = 4 * q + k;
-                if (c < p.C) store_out(g + c * HW + y * p.W + x, (T)(sum[k] / nelems));
-            }
-        }
+        st.step(buf, q, qend);
+        const f4 sum = bwd_quad<D * D>(buf + centre, wp, D * D, [](int t) { return ((t / D) - MD) * CC + (t % D) - MD; });
+        if (inimg) bwd_store_quad(g, y * p.W + x, q, p.C, HW, sum, nelems);
     }
-}
-
-// one batch item is indexed with ints, the grid's y / z extents are 16-bit
-bool dense_fits(const CorrP &p)
-{
-    const long HW = (long)p.H * p.W;
-    if (((long)p.C + 4) * HW >= (1L << 31) || (long)p.nOut * HW >= (1L << 31)) return false;   // C + 4: the zero-filled tail of the last quad
-    if (p.B > 32767) return false;
-    const long tiles = (long)((p.W + FTW - 1) / FTW) * ((p.H + FTH - 1) / FTH);
-    return tiles < (1L << 31);
 }
 
 template <typename T, int MD>
 int fwd_dense_launch(const void *in1, const void *in2, void *out, const CorrP &p, hipStream_t s)
 {
     const int tilesX = (p.W + FTW - 1) / FTW, tilesY = (p.H + FTH - 1) / FTH;
-    // two results of a lane go out as one store where every row of every plane keeps the pair aligned
-    const int vec = (p.W % 2 == 0) && (p.out_bs % 2 == 0) && aligned(out, 2 * sizeof(T));
+    const int vec = fwd_pairs_aligned(p.W, p.out_bs, out, sizeof(T));
     hipLaunchKernelGGL((corr_fwd_dense<T, MD>), dim3(tilesX * tilesY, 1, p.B), dim3((2 * MD + 1) * 64), 0, s,
                        static_cast<const T *>(in1), static_cast<const T *>(in2), static_cast<T *>(out), p, tilesX, vec);
     return launch_status();
@@ -352,13 +201,8 @@ int bwd_dense_launch(const void *in1, const void *in2, const void *gout, void *g
 {
     const int tilesX = (p.W + BTW - 1) / BTW, tilesY = (p.H + BTH - 1) / BTH;
     const int nq = (p.C + 3) / 4;
-    // split the channels until about four workgroups per CU are in the grid (small maps, many channels)
-    const long base = (long)tilesX * tilesY * p.B * 2;
-    int split = (int)((1024 + base - 1) / base);
-    if (split > nq) split = nq;
-    if (split < 1) split = 1;
-    const int qper = (nq + split - 1) / split;
-    split = (nq + qper - 1) / qper;
+    int split;
+    const int qper = bwd_channel_split((long)tilesX * tilesY * p.B * 2, nq, &split);
     hipLaunchKernelGGL((corr_bwd_dense<T, MD>), dim3(tilesX * tilesY, split, p.B * 2), dim3(BTW * BTH), 0, s,
                        static_cast<const T *>(in1), static_cast<const T *>(in2), static_cast<const T *>(gout),
                        static_cast<T *>(g1), static_cast<T *>(g2), p, tilesX, qper);
@@ -413,7 +257,7 @@ bool corr_dense_forward_pays(const CorrP &p)
 
 int corr_forward_dense(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s)
 {
-    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !dense_fits(p)) return FN2_EUNSUPPORTED;
+    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !tiled_fits(p)) return FN2_EUNSUPPORTED;
     if (p.B == 0) return FN2_OK;
     switch (dtype) {
     case FN2_F32: return fwd_dense_md<float>(in1, in2, out, p, s);
@@ -426,7 +270,7 @@ int corr_forward_dense(const void *in1, const void *in2, void *out, int dtype, c
 int corr_backward_dense(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype, const CorrP &p,
                         hipStream_t s)
 {
-    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !dense_fits(p)) return FN2_EUNSUPPORTED;
+    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !tiled_fits(p)) return FN2_EUNSUPPORTED;
     if (p.B == 0) return FN2_OK;
     switch (dtype) {
     case FN2_F32: return bwd_dense_md<float>(in1, in2, gout, g1, g2, p, s);

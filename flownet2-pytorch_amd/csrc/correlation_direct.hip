@@ -22,7 +22,8 @@
 
 namespace fn2 {
 
-// Acc<T> and fwd_prod<T> (one product of the forward) live in corr_arith.h, shared with correlation_dense.hip
+// Acc<T>, fwd_prod<T> (one product of the forward), fwd_channel_sum<T> (the channel sum of one pixel pair) and stream_grid live in
+// corr_arith.h, shared with correlation_1d.hip's general kernels and the tiled kernels (corr_tiled.h)
 
 // ---------------------------------------------------------------- forward
 template <typename T>
@@ -52,16 +53,7 @@ __global__ __launch_bounds__(256) void corr_fwd_direct(const T *__restrict__ in1
                 if (xa < 0 || xa >= p.W || xb < 0 || xb >= p.W) continue;
                 const T *pa = a + (long)ya * p.W + xa;
                 const T *pb = b + (long)yb * p.W + xb;
-                float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f; // 4 independent chains for ILP
-                int c = 0;
-                for (; c + 4 <= p.C; c += 4) {
-                    s0 += fwd_prod<T>(pa[(long)(c + 0) * HW], pb[(long)(c + 0) * HW]);
-                    s1 += fwd_prod<T>(pa[(long)(c + 1) * HW], pb[(long)(c + 1) * HW]);
-                    s2 += fwd_prod<T>(pa[(long)(c + 2) * HW], pb[(long)(c + 2) * HW]);
-                    s3 += fwd_prod<T>(pa[(long)(c + 3) * HW], pb[(long)(c + 3) * HW]);
-                }
-                for (; c < p.C; ++c) s0 += fwd_prod<T>(pa[(long)c * HW], pb[(long)c * HW]);
-                acc += (s0 + s1) + (s2 + s3);
+                acc += fwd_channel_sum<T>(pa, pb, p.C, HW);   // four chains over the channels (corr_arith.h)
             }
         }
         const int nelems = p.k * p.k * p.C;
@@ -135,14 +127,6 @@ __global__ __launch_bounds__(256) void corr_bwd_direct(const T *__restrict__ in1
         g1[idx] = (T)(sum1 / nelems);
         g2[idx] = (T)(sum2 / nelems);
     }
-}
-
-static inline unsigned stream_grid(long nthreads, long cap_blocks)
-{
-    long blocks = (nthreads + 255) / 256;
-    if (blocks > cap_blocks) blocks = cap_blocks;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
 }
 
 int corr_make_params(CorrP &p, int B, int C, int H, int W, int pad, int k, int md, int s1, int s2)
