@@ -1,7 +1,9 @@
 """Builds libflownet2_hip.so (hand-written gfx950 HIP kernels + C ABI) and the three pybind
 modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without hipify; and libflownet2_hip_ext.so
 (include/flownet2_hip_ext.h: layers outside the drop-in boundary, Correlation1d) with its module correlation1d_cuda; and
-libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h: CorrLookup, RAFT's correlation lookup) with its module corr_lookup_cuda.
+libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h: CorrLookup, RAFT's correlation lookup) with its module corr_lookup_cuda; and
+libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h: ConvexUpsample, RAFT's convex flow upsampling) with its module
+convex_upsample_cuda.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -29,9 +31,12 @@ EXT_LIB = os.path.join(LIBDIR, "libflownet2_hip_ext.so")
 EXT_SRCS = ["capi_ext.hip", "correlation_1d.hip"]
 # sibling libraries by name: libflownet2_hip_<name>.so from its sources, csrc/exports_<name>.map and include/flownet2_hip_<name>.h;
 # the same flags, objects under lib/<name>/, and none links another
-SIBLINGS = {"ext": EXT_SRCS, "lookup": ["capi_lookup.hip", "corr_lookup.hip"]}
-MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda", "corr_lookup_cuda"]
-MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext", "corr_lookup_cuda": "flownet2_hip_lookup"}   # every other module links libflownet2_hip.so
+SIBLINGS = {"ext": EXT_SRCS, "lookup": ["capi_lookup.hip", "corr_lookup.hip"],
+            "upsample": ["capi_upsample.hip", "convex_upsample.hip"]}
+MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda", "corr_lookup_cuda",
+           "convex_upsample_cuda"]
+MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext", "corr_lookup_cuda": "flownet2_hip_lookup",
+               "convex_upsample_cuda": "flownet2_hip_upsample"}   # every other module links libflownet2_hip.so
 MAX_JOBS = 16
 
 
@@ -91,7 +96,8 @@ def build_modules(force=False):
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
         deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"), os.path.join(HERE, "..", "include", "flownet2_hip_lookup.h")]
+                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"), os.path.join(HERE, "..", "include", "flownet2_hip_lookup.h"),
+                os.path.join(HERE, "..", "include", "flownet2_hip_upsample.h")]
         if force or not _newer(out, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                    "-DTORCH_EXTENSION_NAME=" + m, "-DTORCH_API_INCLUDE_EXTENSION_H",
@@ -119,7 +125,7 @@ def main():
     a = ap.parse_args()
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=4) as pool:
+    with ThreadPoolExecutor(max_workers=5) as pool:
         futs = [pool.submit(build_lib, a.force, False)] + [pool.submit(build_lib, a.force, ext=name) for name in SIBLINGS]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))

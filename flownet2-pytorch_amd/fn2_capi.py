@@ -48,10 +48,16 @@ LOOKUP_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_lookup.so")
 LOOKUP_EXPORTS = ["fn2l_abi_version", "fn2l_corr_lookup_forward", "fn2l_corr_lookup_backward"]
 FN2L_LOOKUP_AUTO, FN2L_LOOKUP_GENERAL, FN2L_LOOKUP_STAGED = 0, 1, 2
 
+# libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h): ConvexUpsample, RAFT's convex flow upsampling; the fourth library
+UPSAMPLE_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_upsample.so")
+UPSAMPLE_EXPORTS = ["fn2u_abi_version", "fn2u_convex_upsample_forward", "fn2u_convex_upsample_backward",
+                    "fn2u_convex_upsample_backward_workspace_bytes"]
+
 _lib = None
 _dbg = None
 _ext = None
 _lookup = None
+_upsample = None
 
 
 def lib():
@@ -117,6 +123,21 @@ def lookup_lib():
         for name in LOOKUP_EXPORTS:
             getattr(_lookup, name).restype = ctypes.c_int
     return _lookup
+
+
+def upsample_lib():
+    """libflownet2_hip_upsample.so: ConvexUpsample (csrc/convex_upsample.hip).  Self-contained; loads without the other three libraries."""
+    global _upsample
+    if _upsample is None:
+        import torch  # noqa: F401
+        if not os.path.exists(UPSAMPLE_LIB_PATH):
+            raise RuntimeError(f"{UPSAMPLE_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _upsample = ctypes.CDLL(UPSAMPLE_LIB_PATH)
+        for name in UPSAMPLE_EXPORTS:
+            getattr(_upsample, name).restype = ctypes.c_int
+        _upsample.fn2u_convex_upsample_backward_workspace_bytes.restype = ctypes.c_size_t
+    return _upsample
 
 
 def check(rc, what):
@@ -216,6 +237,42 @@ def corr_lookup_backward(fmap1, fmap2, coords, gout, radius, scale, algo=FN2L_LO
                                                      H, W, H2, W2, radius, ctypes.c_float(scale), algo, _stream(fmap1)),
               "fn2l_corr_lookup_backward")
     return g1, g2
+
+
+def _upsample_factor(flow, mask, factor):
+    B, C, H, W = flow.shape
+    assert flow.is_contiguous() and mask.is_contiguous() and tuple(mask.shape) == (B, 9 * factor * factor, H, W)
+    return B, C, H, W
+
+
+def convex_upsample_forward(flow, mask, factor, scale, out=None):
+    """fn2u_convex_upsample_forward on contiguous device tensors (flow float32; mask float32, float16 or bfloat16); ``out``: a
+    preallocated float32 B x C x factor H x factor W result."""
+    import torch
+    B, C, H, W = _upsample_factor(flow, mask, factor)
+    if out is None:
+        out = torch.empty((B, C, factor * H, factor * W), dtype=flow.dtype, device=flow.device)
+    with torch.cuda.device_of(flow):
+        check(upsample_lib().fn2u_convex_upsample_forward(_p(flow), _p(mask), _p(out), _dtype_code(mask), B, C, H, W, factor,
+                                                          ctypes.c_float(scale), _stream(flow)), "fn2u_convex_upsample_forward")
+    return out
+
+
+def convex_upsample_backward(flow, mask, gout, factor, scale, out=None, workspace=None):
+    """fn2u_convex_upsample_backward: (grad_flow, grad_mask); ``out``: the two preallocated gradients (no pre-zeroing needed);
+    ``workspace``: a device buffer of fn2u_convex_upsample_backward_workspace_bytes, allocated here if None."""
+    import torch
+    B, C, H, W = _upsample_factor(flow, mask, factor)
+    assert gout.is_contiguous() and tuple(gout.shape) == (B, C, factor * H, factor * W)
+    gf, gm = out if out is not None else (torch.empty_like(flow), torch.empty_like(mask))
+    if workspace is None:
+        nbytes = upsample_lib().fn2u_convex_upsample_backward_workspace_bytes(B, C, H, W)
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=flow.device)
+    with torch.cuda.device_of(flow):
+        check(upsample_lib().fn2u_convex_upsample_backward(_p(flow), _p(mask), _p(gout), _p(gf), _p(gm), _p(workspace), _dtype_code(mask),
+                                                           B, C, H, W, factor, ctypes.c_float(scale), _stream(flow)),
+              "fn2u_convex_upsample_backward")
+    return gf, gm
 
 
 def correlation_forward_fused(in1, in2, buffer, channel_offset, negative_slope, pad, k, md, s1, s2, algo=FN2_CORR_AUTO):
