@@ -53,11 +53,18 @@ UPSAMPLE_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_upsample.so")
 UPSAMPLE_EXPORTS = ["fn2u_abi_version", "fn2u_convex_upsample_forward", "fn2u_convex_upsample_backward",
                     "fn2u_convex_upsample_backward_workspace_bytes"]
 
+# libflownet2_hip_splat.so (include/flownet2_hip_splat.h): ForwardWarp, forward flow splatting; the fifth library
+SPLAT_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_splat.so")
+SPLAT_EXPORTS = ["fn2s_abi_version", "fn2s_forward_warp_forward", "fn2s_forward_warp_forward_det_workspace_bytes",
+                 "fn2s_forward_warp_forward_det", "fn2s_forward_warp_backward"]
+FN2S_AUTO, FN2S_GENERAL, FN2S_TILED = 0, 1, 2
+
 _lib = None
 _dbg = None
 _ext = None
 _lookup = None
 _upsample = None
+_splat = None
 
 
 def lib():
@@ -138,6 +145,22 @@ def upsample_lib():
             getattr(_upsample, name).restype = ctypes.c_int
         _upsample.fn2u_convex_upsample_backward_workspace_bytes.restype = ctypes.c_size_t
     return _upsample
+
+
+def splat_lib():
+    """libflownet2_hip_splat.so: ForwardWarp (csrc/forward_warp.hip).  Self-contained; loads without the other four libraries."""
+    global _splat
+    if _splat is None:
+        import torch  # noqa: F401
+        if not os.path.exists(SPLAT_LIB_PATH):
+            raise RuntimeError(f"{SPLAT_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _splat = ctypes.CDLL(SPLAT_LIB_PATH)
+        for name in SPLAT_EXPORTS:
+            getattr(_splat, name).restype = ctypes.c_int
+        _splat.fn2s_forward_warp_forward_det_workspace_bytes.restype = ctypes.c_size_t
+        _splat.fn2s_forward_warp_forward_det.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+    return _splat
 
 
 def check(rc, what):
@@ -452,3 +475,51 @@ def multiscale_l1_epe(outputs, target, weights, start_scale=4, div_flow=0.05, wa
                                         start_scale, n, ctypes.c_float(div_flow), _p(ws), ctypes.c_size_t(wsb),
                                         _stream(target)), "fn2_multiscale_loss")
     return sums, grads
+
+
+def _splat_shape(inp, flow):
+    B, C, H, W = inp.shape
+    assert inp.is_contiguous() and flow.is_contiguous() and tuple(flow.shape) == (B, 2, H, W)
+    return B, C, H, W
+
+
+def forward_warp_forward(inp, flow, algo=FN2S_AUTO, out=None):
+    """fn2s_forward_warp_forward on contiguous float32 device tensors; ``algo``: FN2S_AUTO / _GENERAL / _TILED; ``out``: a
+    preallocated result (cleared by the entry point)."""
+    import torch
+    B, C, H, W = _splat_shape(inp, flow)
+    if out is None:
+        out = torch.empty_like(inp)
+    with torch.cuda.device_of(inp):
+        check(splat_lib().fn2s_forward_warp_forward(_p(inp), _p(flow), _p(out), B, C, H, W, algo, _stream(inp)), "fn2s_forward_warp_forward")
+    return out
+
+
+def forward_warp_forward_det(inp, flow, out=None, workspace=None):
+    """fn2s_forward_warp_forward_det; ``workspace``: a device buffer of fn2s_forward_warp_forward_det_workspace_bytes (no
+    initialisation needed), allocated here if None."""
+    import torch
+    B, C, H, W = _splat_shape(inp, flow)
+    if out is None:
+        out = torch.empty_like(inp)
+    if workspace is None:
+        nbytes = splat_lib().fn2s_forward_warp_forward_det_workspace_bytes(B, C, H, W)
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=inp.device)
+    with torch.cuda.device_of(inp):
+        check(splat_lib().fn2s_forward_warp_forward_det(_p(inp), _p(flow), _p(out), _p(workspace), workspace.numel() * workspace.element_size(),
+                                                        B, C, H, W, _stream(inp)), "fn2s_forward_warp_forward_det")
+    return out
+
+
+def forward_warp_backward(inp, flow, gout, want_input=True, want_flow=True):
+    """fn2s_forward_warp_backward: (grad_input, grad_flow), None for one that is not wanted (its pointer is passed as NULL)."""
+    import torch
+    B, C, H, W = _splat_shape(inp, flow)
+    assert gout.is_contiguous() and gout.shape == inp.shape
+    gi = torch.empty_like(inp) if want_input else None
+    gf = torch.empty_like(flow) if want_flow else None
+    null = ctypes.c_void_p(0)
+    with torch.cuda.device_of(inp):
+        check(splat_lib().fn2s_forward_warp_backward(_p(inp), _p(flow), _p(gout), _p(gi) if want_input else null, _p(gf) if want_flow else null,
+                                                     B, C, H, W, _stream(inp)), "fn2s_forward_warp_backward")
+    return gi, gf
