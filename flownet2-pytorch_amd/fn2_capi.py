@@ -59,12 +59,17 @@ SPLAT_EXPORTS = ["fn2s_abi_version", "fn2s_forward_warp_forward", "fn2s_forward_
                  "fn2s_forward_warp_forward_det", "fn2s_forward_warp_backward"]
 FN2S_AUTO, FN2S_GENERAL, FN2S_TILED = 0, 1, 2
 
+# libflownet2_hip_census.so (include/flownet2_hip_census.h): the ternary census distance; the sixth library
+CENSUS_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_census.so")
+CENSUS_EXPORTS = ["fn2c_abi_version", "fn2c_census_forward", "fn2c_census_backward"]
+
 _lib = None
 _dbg = None
 _ext = None
 _lookup = None
 _upsample = None
 _splat = None
+_census = None
 
 
 def lib():
@@ -161,6 +166,22 @@ def splat_lib():
         _splat.fn2s_forward_warp_forward_det_workspace_bytes.restype = ctypes.c_size_t
         _splat.fn2s_forward_warp_forward_det.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     return _splat
+
+
+def census_lib():
+    """libflownet2_hip_census.so: the ternary census distance (csrc/census.hip).  Self-contained; loads without the other five libraries."""
+    global _census
+    if _census is None:
+        import torch  # noqa: F401
+        if not os.path.exists(CENSUS_LIB_PATH):
+            raise RuntimeError(f"{CENSUS_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _census = ctypes.CDLL(CENSUS_LIB_PATH)
+        for name in CENSUS_EXPORTS:
+            getattr(_census, name).restype = ctypes.c_int
+        _census.fn2c_census_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+        _census.fn2c_census_backward.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+    return _census
 
 
 def check(rc, what):
@@ -523,3 +544,36 @@ def forward_warp_backward(inp, flow, gout, want_input=True, want_flow=True):
         check(splat_lib().fn2s_forward_warp_backward(_p(inp), _p(flow), _p(gout), _p(gi) if want_input else null, _p(gf) if want_flow else null,
                                                      B, C, H, W, _stream(inp)), "fn2s_forward_warp_backward")
     return gi, gf
+
+
+def _census_shape(im1, im2):
+    N, C, H, W = im1.shape
+    assert im1.is_contiguous() and im2.is_contiguous() and im2.shape == im1.shape
+    return N, C, H, W
+
+
+def census_forward(im1, im2, max_distance=3, scale=255.0, normalize=True, out=None):
+    """fn2c_census_forward on contiguous float32 device tensors; ``out``: a preallocated N x 1 x H x W result (fully written)."""
+    import torch
+    N, C, H, W = _census_shape(im1, im2)
+    if out is None:
+        out = torch.empty((N, 1, H, W), dtype=im1.dtype, device=im1.device)
+    with torch.cuda.device_of(im1):
+        check(census_lib().fn2c_census_forward(_p(im1), _p(im2), _p(out), N, C, H, W, int(max_distance), float(scale), 1 if normalize else 0,
+                                               _stream(im1)), "fn2c_census_forward")
+    return out
+
+
+def census_backward(im1, im2, gout, max_distance=3, scale=255.0, normalize=True, want1=True, want2=True, grads=(None, None)):
+    """fn2c_census_backward: (grad_im1, grad_im2), None for one that is not wanted (its pointer is passed as NULL); ``grads``:
+    preallocated results."""
+    import torch
+    N, C, H, W = _census_shape(im1, im2)
+    assert gout.is_contiguous() and tuple(gout.shape) == (N, 1, H, W)
+    g1 = (grads[0] if grads[0] is not None else torch.empty_like(im1)) if want1 else None
+    g2 = (grads[1] if grads[1] is not None else torch.empty_like(im2)) if want2 else None
+    null = ctypes.c_void_p(0)
+    with torch.cuda.device_of(im1):
+        check(census_lib().fn2c_census_backward(_p(im1), _p(im2), _p(gout), _p(g1) if want1 else null, _p(g2) if want2 else null, N, C, H, W,
+                                                int(max_distance), float(scale), 1 if normalize else 0, _stream(im1)), "fn2c_census_backward")
+    return g1, g2

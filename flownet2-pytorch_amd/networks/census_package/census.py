@@ -1,0 +1,88 @@
+"""The ternary census distance, the photometric term of unsupervised optical flow (UnFlow, ARFlow, UFlow, SMURF), as an autograd
+Function + Modules over the ``census_cuda`` extension (csrc/binding/census_cuda.cpp, csrc/census.hip).
+
+    g = grey(im) * scale        t_k(p) = f(g[p + k] - g[p]),  f(x) = x / sqrt(0.81 + x^2)        k over the (2 md + 1)^2 patch
+    dist[n, 0, p] = mean_k (or sum_k) h(t1_k(p) - t2_k(p)),   h(d) = d^2 / (0.1 + d^2)           exactly 0 on the border ring of width md
+
+``im1`` and ``im2`` are float32 N x C x H x W with C = 1 or 3; the result is N x 1 x H x W.  Both images get gradients; the
+backward is a gather without atomics and bit-reproducible.  One kernel each way replaces the composition's 49-channel unfold and
+its N x 49 x H x W temporaries.  Semantics, arithmetic order and bounds are documented in include/flownet2_hip_census.h.
+Importing this module fails loudly if the extension has not been built: the HIP kernels are the only implementation.
+"""
+import torch
+from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+import census_cuda  # built by flownet2-pytorch_amd/build.py; no fallback on purpose
+
+
+class CensusFunction(Function):
+    """``apply`` goes straight to the autograd node the extension implements in C++ (``census_cuda.apply``);
+    ``forward`` / ``backward`` are the same two calls for code that drives a Function's static methods itself."""
+
+    @classmethod
+    def apply(cls, im1, im2, max_distance=3, scale=255.0, normalize=True):
+        return census_cuda.apply(im1, im2, int(max_distance), float(scale), bool(normalize))
+
+    @staticmethod
+    def forward(ctx, im1, im2, max_distance=3, scale=255.0, normalize=True):
+        ctx.save_for_backward(im1, im2)
+        ctx.options = (int(max_distance), float(scale), bool(normalize))
+        return census_cuda.forward_alloc(im1, im2, *ctx.options)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        im1, im2 = ctx.saved_tensors
+        want1, want2 = ctx.needs_input_grad[:2]
+        if not (want1 or want2):
+            return None, None, None, None, None
+        return tuple(census_cuda.backward_alloc(im1, im2, grad_output, *ctx.options, want1, want2)) + (None, None, None)
+
+
+def census_distance(im1, im2, max_distance=3, scale=255.0, normalize=True):
+    """N x 1 x H x W: the soft Hamming distance of the two images' ternary census signatures; ``normalize`` picks the mean over
+    the patch (ARFlow) or the sum (UFlow)."""
+    return CensusFunction.apply(im1, im2, max_distance, scale, normalize)
+
+
+class TernaryCensus(nn.Module):
+    """``TernaryCensus(max_distance=3)(im1, im2)`` -> N x 1 x H x W, ``census_distance`` with the parameters kept in the module."""
+
+    def __init__(self, max_distance=3, scale=255.0, normalize=True):
+        super().__init__()
+        if max_distance not in (1, 2, 3):
+            raise ValueError(f"TernaryCensus: max_distance {max_distance!r} is not 1, 2 or 3")
+        self.max_distance, self.scale, self.normalize = int(max_distance), float(scale), bool(normalize)
+
+    def forward(self, im1, im2):
+        return CensusFunction.apply(im1, im2, self.max_distance, self.scale, self.normalize)
+
+    def extra_repr(self):
+        return f"max_distance={self.max_distance}, scale={self.scale}, normalize={self.normalize}"
+
+
+class CensusLoss(nn.Module):
+    """The photometric loss of ARFlow / UnFlow: ``loss(im1, im2_warped, mask=None)`` ->
+
+        sum((dist + eps)^q * valid) / (sum(valid) + 1e-6),        valid = the inner rectangle (the border ring removed) * mask
+
+    ``mask`` is N x 1 x H x W (an occlusion mask, 1 = use the pixel) or None.  The distance is the HIP kernel; the robust function
+    and the reduction act on one plane and stay in PyTorch."""
+
+    def __init__(self, max_distance=3, q=0.4, eps=0.01, scale=255.0):
+        super().__init__()
+        self.census = TernaryCensus(max_distance, scale, True)
+        self.q, self.eps = float(q), float(eps)
+
+    def forward(self, im1, im2_warped, mask=None):
+        dist = self.census(im1, im2_warped)
+        md = self.census.max_distance
+        valid = torch.zeros_like(dist)
+        valid[:, :, md:dist.shape[2] - md, md:dist.shape[3] - md] = 1.0
+        if mask is not None:
+            if mask.shape != dist.shape:
+                raise ValueError(f"CensusLoss: mask of shape {tuple(mask.shape)} must be N x 1 x H x W = {tuple(dist.shape)}")
+            valid = valid * mask
+        return ((dist + self.eps) ** self.q * valid).sum() / (valid.sum() + 1e-6)
