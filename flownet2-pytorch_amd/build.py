@@ -4,7 +4,8 @@ modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without 
 libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h: CorrLookup, RAFT's correlation lookup) with its module corr_lookup_cuda; and
 libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h: ConvexUpsample, RAFT's convex flow upsampling) with its module
 convex_upsample_cuda; and libflownet2_hip_splat.so (include/flownet2_hip_splat.h: ForwardWarp, forward flow splatting) with its module
-forward_warp_cuda; and libflownet2_hip_census.so (include/flownet2_hip_census.h: the ternary census distance) with its module census_cuda.
+forward_warp_cuda; and libflownet2_hip_census.so (include/flownet2_hip_census.h: the ternary census distance) with its module census_cuda;
+and libflownet2_hip_smooth.so (include/flownet2_hip_smooth.h: the edge-aware smoothness term) with its module smoothness_cuda.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -34,12 +35,12 @@ EXT_SRCS = ["capi_ext.hip", "correlation_1d.hip"]
 # the same flags, objects under lib/<name>/, and none links another
 SIBLINGS = {"ext": EXT_SRCS, "lookup": ["capi_lookup.hip", "corr_lookup.hip"],
             "upsample": ["capi_upsample.hip", "convex_upsample.hip"], "splat": ["capi_splat.hip", "forward_warp.hip"],
-            "census": ["capi_census.hip", "census.hip"]}
+            "census": ["capi_census.hip", "census.hip"], "smooth": ["capi_smooth.hip", "smooth.hip"]}
 MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda", "corr_lookup_cuda",
-           "convex_upsample_cuda", "forward_warp_cuda", "census_cuda"]
+           "convex_upsample_cuda", "forward_warp_cuda", "census_cuda", "smoothness_cuda"]
 MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext", "corr_lookup_cuda": "flownet2_hip_lookup",
                "convex_upsample_cuda": "flownet2_hip_upsample", "forward_warp_cuda": "flownet2_hip_splat",
-               "census_cuda": "flownet2_hip_census"}   # every other module links libflownet2_hip.so
+               "census_cuda": "flownet2_hip_census", "smoothness_cuda": "flownet2_hip_smooth"}   # every other module links libflownet2_hip.so
 MAX_JOBS = 16
 
 
@@ -101,7 +102,7 @@ def build_modules(force=False):
         deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h"),
                 os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"), os.path.join(HERE, "..", "include", "flownet2_hip_lookup.h"),
                 os.path.join(HERE, "..", "include", "flownet2_hip_upsample.h"), os.path.join(HERE, "..", "include", "flownet2_hip_splat.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_census.h")]
+                os.path.join(HERE, "..", "include", "flownet2_hip_census.h"), os.path.join(HERE, "..", "include", "flownet2_hip_smooth.h")]
         if force or not _newer(out, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                    "-DTORCH_EXTENSION_NAME=" + m, "-DTORCH_API_INCLUDE_EXTENSION_H",
@@ -129,7 +130,7 @@ def main():
     a = ap.parse_args()
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=7) as pool:
+    with ThreadPoolExecutor(max_workers=8) as pool:
         futs = [pool.submit(build_lib, a.force, False)] + [pool.submit(build_lib, a.force, ext=name) for name in SIBLINGS]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))

@@ -63,6 +63,11 @@ FN2S_AUTO, FN2S_GENERAL, FN2S_TILED = 0, 1, 2
 CENSUS_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_census.so")
 CENSUS_EXPORTS = ["fn2c_abi_version", "fn2c_census_forward", "fn2c_census_backward"]
 
+# libflownet2_hip_smooth.so (include/flownet2_hip_smooth.h): the edge-aware smoothness term; the seventh library
+SMOOTH_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_smooth.so")
+SMOOTH_EXPORTS = ["fn2m_abi_version", "fn2m_smoothness_forward", "fn2m_smoothness_backward"]
+FN2M_EDGE = {"exponential": 0, "gaussian": 1}
+
 _lib = None
 _dbg = None
 _ext = None
@@ -70,6 +75,7 @@ _lookup = None
 _upsample = None
 _splat = None
 _census = None
+_smooth = None
 
 
 def lib():
@@ -182,6 +188,22 @@ def census_lib():
         _census.fn2c_census_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
         _census.fn2c_census_backward.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
     return _census
+
+
+def smooth_lib():
+    """libflownet2_hip_smooth.so: the edge-aware smoothness term (csrc/smooth.hip).  Self-contained; loads without the other six libraries."""
+    global _smooth
+    if _smooth is None:
+        import torch  # noqa: F401
+        if not os.path.exists(SMOOTH_LIB_PATH):
+            raise RuntimeError(f"{SMOOTH_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
+                               "(the HIP kernels are the only implementation)")
+        _smooth = ctypes.CDLL(SMOOTH_LIB_PATH)
+        for name in SMOOTH_EXPORTS:
+            getattr(_smooth, name).restype = ctypes.c_int
+        _smooth.fn2m_smoothness_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+        _smooth.fn2m_smoothness_backward.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+    return _smooth
 
 
 def check(rc, what):
@@ -577,3 +599,34 @@ def census_backward(im1, im2, gout, max_distance=3, scale=255.0, normalize=True,
         check(census_lib().fn2c_census_backward(_p(im1), _p(im2), _p(gout), _p(g1) if want1 else null, _p(g2) if want2 else null, N, C, H, W,
                                                 int(max_distance), float(scale), 1 if normalize else 0, _stream(im1)), "fn2c_census_backward")
     return g1, g2
+
+
+def _smooth_shape(flow, image):
+    N, F, H, W = flow.shape
+    assert flow.is_contiguous() and image.is_contiguous() and image.shape[0] == N and tuple(image.shape[2:]) == (H, W)
+    return N, F, image.shape[1], H, W
+
+
+def smoothness_forward(flow, image, order=1, edge_weighting="exponential", alpha=150.0, eps=0.001, out=None):
+    """fn2m_smoothness_forward on contiguous float32 device tensors; ``out``: a preallocated N x 2 x H x W result (fully written)."""
+    import torch
+    N, F, C, H, W = _smooth_shape(flow, image)
+    if out is None:
+        out = torch.empty((N, 2, H, W), dtype=flow.dtype, device=flow.device)
+    with torch.cuda.device_of(flow):
+        check(smooth_lib().fn2m_smoothness_forward(_p(flow), _p(image), _p(out), N, F, C, H, W, int(order), FN2M_EDGE[edge_weighting],
+                                                   float(alpha), float(eps), _stream(flow)), "fn2m_smoothness_forward")
+    return out
+
+
+def smoothness_backward(flow, image, gout, order=1, edge_weighting="exponential", alpha=150.0, eps=0.001, out=None):
+    """fn2m_smoothness_backward: grad_flow; ``out``: a preallocated N x F x H x W result (fully written)."""
+    import torch
+    N, F, C, H, W = _smooth_shape(flow, image)
+    assert gout.is_contiguous() and tuple(gout.shape) == (N, 2, H, W)
+    if out is None:
+        out = torch.empty_like(flow)
+    with torch.cuda.device_of(flow):
+        check(smooth_lib().fn2m_smoothness_backward(_p(flow), _p(image), _p(gout), _p(out), N, F, C, H, W, int(order), FN2M_EDGE[edge_weighting],
+                                                    float(alpha), float(eps), _stream(flow)), "fn2m_smoothness_backward")
+    return out
