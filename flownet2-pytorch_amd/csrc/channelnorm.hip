@@ -28,6 +28,10 @@ template <typename T> __device__ __forceinline__ float chnorm_sq(T v)
     else return (float)(T)(v * v);
 }
 
+// the root of the sum (:58): sqrtf, correctly rounded like the reference's sqrt(float).  Not __fsqrt_rn: despite its name that is HIP's
+// native square root, which the compiler may expand to the bare v_sqrt_f32 (1 ulp) -- it did in the vector kernel, not in the scalar one.
+__device__ __forceinline__ float chnorm_root(float acc) { return sqrtf(acc); }
+
 // ---------------------------------------------------------------- forward
 // grid-stride over "pixel groups" of N pixels; HW % N == 0 guaranteed by the launcher.
 template <typename T>
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(256) void chnorm_fwd_vec(const T *__restrict__ in, 
         }
         V o;
 #pragma unroll
-        for (int i = 0; i < N; ++i) o[i] = (T)__fsqrt_rn(acc[i]);
+        for (int i = 0; i < N; ++i) o[i] = (T)chnorm_root(acc[i]);
         store_out(reinterpret_cast<V *>(out + b * HW + p), o);
     }
 }
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(256) void chnorm_fwd_scalar(const T *__restrict__ i
         for (int c = 0; c < C; ++c) {
             acc = acc + chnorm_sq<T>(src[(long)c * HW]);
         }
-        out[g] = (T)__fsqrt_rn(acc);
+        out[g] = (T)chnorm_root(acc);
     }
 }
 

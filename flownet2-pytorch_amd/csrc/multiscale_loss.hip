@@ -120,6 +120,8 @@ __global__ __launch_bounds__(256) void multiscale_l1_epe_kernel(MsArgs p)
                 const float d0 = o0[i] - lv[cur][0][tid] / inv;
                 const float d1 = o1[i] - lv[cur][1][tid] / inv;
                 l1[i] = fabsf(d0) + fabsf(d1);
+                // (__fsqrt_rn is HIP's native square root: within 1 ulp, not necessarily correctly rounded -- channelnorm.hip's chnorm_root
+                // tells what that cost there; whether it matters here has not been examined)
                 ep[i] = __fsqrt_rn(d0 * d0 + d1 * d1);
                 if (p.grad[i]) {
                     if (p.norm == 2) {

@@ -470,7 +470,7 @@ __global__ __launch_bounds__(1024, 8) void resample_fwd_tiled(const float *__res
             if (!(flags[k] & LIVE)) continue;
             const int pix = y * W + x;
             if (FUSE == 2) {                                            // only ||first image - warped||: B x 1 x H x W
-                store_out(out + (long)b * HW + pix, __fsqrt_rn(ssq[k]));
+                store_out(out + (long)b * HW + pix, sqrtf(ssq[k]));
                 continue;
             }
             float *ob = out + (long)b * (3 * C + 3) * HW + pix;
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(1024, 8) void resample_fwd_tiled(const float *__res
             const float inv_div = 1.0f / div_flow;
             store_out(ob + (long)(3 * C) * HW, flow[(long)b * 2 * HW + pix] * inv_div);
             store_out(ob + (long)(3 * C + 1) * HW, flow[(long)b * 2 * HW + HW + pix] * inv_div);
-            store_out(ob + (long)(3 * C + 2) * HW, __fsqrt_rn(ssq[k]));                      // channelnorm_kernel.cu:52
+            store_out(ob + (long)(3 * C + 2) * HW, sqrtf(ssq[k]));                      // channelnorm_kernel.cu:52
         }
     }
 }
@@ -1514,11 +1514,11 @@ __global__ __launch_bounds__(256) void warp_diff_norm_cat_kernel(const float *__
             const float d = v0 - val;
             ssq = ssq + d * d;
         }
-        if (norm_only) { out[(long)b * HW + pix] = __fsqrt_rn(ssq); continue; }
+        if (norm_only) { out[(long)b * HW + pix] = sqrtf(ssq); continue; }
         const float inv_div = 1.0f / div_flow;   // as PyTorch divides a GPU tensor by a scalar
         ob[(long)(3 * C) * HW] = dx * inv_div;
         ob[(long)(3 * C + 1) * HW] = dy * inv_div;
-        ob[(long)(3 * C + 2) * HW] = __fsqrt_rn(ssq);
+        ob[(long)(3 * C + 2) * HW] = sqrtf(ssq);
     }
 }
 

@@ -28,7 +28,10 @@ __device__ __forceinline__ int d2i_sat(double v)
 
 // The forward's bilinear sample (resample2d_kernel.cu:56-59), the one copy the kernels of both files call: weights in double from the
 // fp32 alpha / beta ("1." literals), each term rounded to float, float accumulation from 0 in the order TL, TR, BL, BR.  Kernels that
-// gather several channels with one position form the weights once (bilinear_weights) and pass them on.
+// gather several channels with one position form the weights once (bilinear_weights) and pass them on.  One term is NOT the reference's
+// arithmetic to the bit: its BR term `(alpha) * (beta) * I` (:59) has no double literal and is formed in fp32 with two roundings, where
+// w11 here is the double product like the other three (one rounding, closer to the exact value).  tests/test_gpu_warp_contract.py pins
+// this sequence bit for bit and counts the elements that differ from the reference's.
 struct BilinearW { double w00, w01, w10, w11; };
 __device__ __forceinline__ BilinearW bilinear_weights(float alpha, float beta)
 {

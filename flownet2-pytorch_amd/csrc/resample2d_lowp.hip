@@ -49,38 +49,14 @@ __device__ __forceinline__ void put4(u4 &v, int j, unsigned w)
     v[0] = j == 0 ? w : v[0]; v[1] = j == 1 ? w : v[1]; v[2] = j == 2 ? w : v[2]; v[3] = j == 3 ? w : v[3];
 }
 
-// The norm's square root.  `__fsqrt_rn` is the "native" square root, which the compiler expands in one of two ways, and it does not pick
-// the same one in every float32 kernel of resample2d.hip: the LDS-window forward kernels (resample_fwd_tiled<.., FUSE>) got the bare
-// v_sqrt_f32 (1 ulp) behind a denormal pre-scale, the one-lane kernel (warp_diff_norm_cat_kernel) the correctly rounded refinement of it.
-// The two differ in the last bit for a small share of inputs, so "the bits of the float32 entry point" depends on which kernel that entry
-// point takes for the shape.  Both expansions are written out here, instruction for instruction, and the launcher selects the one
-// the float32 forward uses for the same shape (the float32 backward reads the forward's norm).
-__device__ __forceinline__ float sqrt_native(float x)
-{
-    const bool sc = x < 0x1.0p-126f;
-    const float r = __builtin_amdgcn_sqrtf(sc ? x * 0x1.0p+32f : x);
-    return sc ? r * 0x1.0p-16f : r;
-}
-__device__ __forceinline__ float sqrt_rounded(float x)
-{
-    const bool sc = x < 0x1.0p-96f;
-    const float xs = sc ? x * 0x1.0p+32f : x;
-    const float s = __builtin_amdgcn_sqrtf(xs);
-    const float dn = __int_as_float(__float_as_int(s) - 1), up = __int_as_float(__float_as_int(s) + 1);
-    const float vp = __builtin_fmaf(-dn, s, xs), vs = __builtin_fmaf(-up, s, xs);
-    float r = (vp <= 0.0f) ? dn : s;
-    r = (vs > 0.0f) ? up : r;
-    r = sc ? r * 0x1.0p-16f : r;
-    return (xs == 0.0f || xs == __builtin_inff()) ? xs : r;
-}
-
+// The norm's square root is sqrtf, correctly rounded, as in the float32 kernels (channelnorm.hip, resample2d.hip): every path has the bits
+// of the float32 entry point on the widened inputs, whichever kernel that entry point takes for the shape.
 // MODE 0: fn2_warp_diff_norm_cat_16   1: fn2_warp_diff_norm_16   2: fn2_warp_diff_norm_cat_backward_16   3: fn2_warp_diff_norm_backward_16
 struct Warp16Args {
     const us *pair, *flow;
     const us *grad;            // MODE 2: B x (3C+3) x H x W concat gradient; MODE 3: B x 1 x H x W gradient of the norm
     us *out;                   // MODE 0: B x (3C+3) x H x W; MODE 1: B x 1 x H x W; MODE 2, 3: B x 2 x H x W flow gradient
     int B, C, H, W, tiles_x, tiles_y, bilinear;
-    int native_sqrt;           // the float32 forward takes its LDS-window kernel for this shape (sqrt_native above)
     float inv_div_flow;
 };
 
@@ -174,7 +150,7 @@ __global__ __launch_bounds__(256) void warp16_tiled(const Warp16Args p)
             diff[c] = Lowp<T>::widen(bfirst[c]) - val[c];   // models.py:134
             ssq = ssq + diff[c] * diff[c];                  // channelnorm_kernel.cu:47-50
         }
-        nrm = sqrt_native(ssq);                             // channelnorm_kernel.cu:52; tileable here = tileable in float32
+        nrm = sqrtf(ssq);                                   // channelnorm_kernel.cu:52
         if constexpr (BWD) {
             const float gnk = Lowp<T>::widen(bgn);
             const float gam_y = 1 - q.alpha, gam_x = 1 - q.beta;      // (:169, :182)
@@ -287,7 +263,7 @@ __global__ __launch_bounds__(256) void warp16_pixel(const Warp16Args p, long npi
                 ob[(long)(2 * C + c) * HW] = narrow<T>(val);
             }
         }
-        const float nrm = p.native_sqrt ? sqrt_native(ssq) : sqrt_rounded(ssq);
+        const float nrm = sqrtf(ssq);
         if constexpr (MODE == 0) {
             us *ob = p.out + (long)b * CC * HW + pix;
             ob[(long)(3 * C) * HW] = narrow<T>(dx * p.inv_div_flow);
@@ -349,8 +325,6 @@ static int warp16(const void *pair, const void *flow, const void *grad, void *ou
     a.out = static_cast<us *>(out);
     a.B = B; a.C = C; a.H = H; a.W = W; a.tiles_x = (W + 63) / 64; a.tiles_y = (H + 31) / 32; a.bilinear = bilinear != 0 ? 1 : 0;
     a.inv_div_flow = 1.0f / div_flow;   // as PyTorch divides a GPU tensor by a scalar
-    // fn2_warp_diff_norm_cat / fn2_warp_diff_norm on the widened tensors (a fresh, 16-byte aligned copy): tiled for these shapes, any C
-    a.native_sqrt = (W % 4 == 0 && H >= 16 && W >= 32) ? 1 : 0;
     const bool tiled = C == 3 && H >= 16 && W >= 32 && W % 8 == 0 && aligned(pair, 16) && aligned(flow, 16) && aligned(out, 16) &&
                        (MODE < 2 || aligned(grad, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);

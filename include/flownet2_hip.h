@@ -362,10 +362,9 @@ int fn2_warp_diff_norm_backward(const float *pair, const float *flow, const floa
  * by the float32 entry points, pointers for 2-byte alignment (FN2_EALIGN), before anything is launched.  C = 3 on maps with
  * H >= 16, W >= 32, W % 8 == 0 and 16-byte aligned tensors takes the LDS-window kernels (eight pixels per lane, 16-byte loads and
  * stores), everything else one lane per pixel; the results do not depend on which.  kernel_size 1.
- * "The float32 entry point on the widened inputs" means on a contiguous, 16-byte aligned float32 copy.  This matters in one place: the
- * float32 forward's LDS-window kernel (maps with H >= 16, W >= 32, W % 4 == 0) takes the norm's square root with the bare v_sqrt_f32
- * (1 ulp), its one-lane kernel with the correctly rounded refinement, and the two differ in the last bit for a small share of sums.
- * The 16-bit entry points use, on every path, the square root the float32 forward uses for the same shape. */
+ * "The float32 entry point on the widened inputs" means on a contiguous, 16-byte aligned float32 copy.  The norm's square root is
+ * correctly rounded in every kernel of either precision (the reference's sqrt(float)), so the results do not depend on which kernel
+ * a shape takes. */
 int fn2_warp_diff_norm_cat_16(const void *pair, const void *flow, void *out, int dtype, float div_flow,
                               int B, int C, int H, int W, int bilinear, void *stream);
 int fn2_warp_diff_norm_cat_backward_16(const void *pair, const void *flow, const void *grad_cat, void *grad_flow, int dtype,

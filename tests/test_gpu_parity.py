@@ -5,7 +5,8 @@ C ABI, against the CPU oracle on identical seeded inputs and against the committ
 Tolerance: BASELINE.json's north star states <= 1e-4 fp32 max-abs.  TOL below is that bound; most
 paths are far tighter (channelnorm and the resample2d gathers restate the reference's operation
 order and are checked at 1e-6; the atomically-scattered resample grad_img and the MFMA correlation,
-whose summation order differs from the reference's 32-lane tree, get the full budget)."""
+whose summation order differs from the reference's 32-lane tree, get the full budget).
+The float32 warp and norm kernels are pinned per element, against float64 and bit for bit, in tests/test_gpu_warp_contract.py."""
 import os
 
 import numpy as np
