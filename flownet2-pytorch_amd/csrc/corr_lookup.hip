@@ -464,16 +464,15 @@ int bwd_launch(const float *f1, const float *f2, const float *co, const float *g
                hipStream_t s)
 {
     constexpr int NP = R <= 4 ? 64 : 32, NY = 256 / NP;
-    hipError_t e = hipMemsetAsync(g2, 0, (size_t)p.B * p.C * p.H2 * p.W2 * sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
+    int rc = zero_fill_async(g2, (size_t)p.B * p.C * p.H2 * p.W2 * sizeof(float), s);
+    if (rc != FN2_OK) return rc;
     if constexpr (R <= FN2L_STAGED_MAX_RADIUS) {
         if (staged) hipLaunchKernelGGL((lookup_g1_staged<R>), dim3(blocks_tiled(p)), dim3(64, CK), 0, s, f2, co, go, g1, p);
         else hipLaunchKernelGGL((lookup_g1_general<R, NP, NY>), dim3(blocks_linear(p, NP)), dim3(NP, NY), 0, s, f2, co, go, g1, p);
     } else {
         hipLaunchKernelGGL((lookup_g1_general<R, NP, NY>), dim3(blocks_linear(p, NP)), dim3(NP, NY), 0, s, f2, co, go, g1, p);
     }
-    int rc = launch_status();
-    if (rc != FN2_OK) return rc;
+    if ((rc = launch_status()) != FN2_OK) return rc;
     hipLaunchKernelGGL((lookup_g2_scatter<R, NP, NY>), dim3(blocks_linear(p, NP)), dim3(NP, NY), 0, s, f1, co, go, g2, p);
     return launch_status();
 }

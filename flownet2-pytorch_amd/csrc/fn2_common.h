@@ -20,6 +20,32 @@ static inline int launch_status()
 
 static inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// Zero fill of n 32-bit words at a 4-byte aligned address, as a kernel: words up to the first 16-byte boundary, 16-byte stores, the
+// last words.  The libraries clear what their atomics add into with this, not with hipMemsetAsync.  Observed, not explained: captured
+// into a hipGraph through torch.cuda.graph on this runtime, the hipMemsetAsync of these buffers did not clear them on replay
+// (tests/test_gpu_pipelines.py: the scatters then added onto uninitialised memory or onto the last replay's sums), while the same
+// call outside a graph always did; why the memset node fails has not been found.  A kernel node replays like the kernels around it.
+template <int = 0> __global__ void __launch_bounds__(256) zero_fill_kernel(unsigned *p, size_t n)
+{
+    const size_t to16 = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;
+    const size_t head = to16 < n ? to16 : n, nv = (n - head) / 4, done = head + 4 * nv;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    uint4 *v = reinterpret_cast<uint4 *>(p + head);
+    for (size_t i = tid; i < nv; i += stride) v[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < head) p[tid] = 0u;
+    if (tid < n - done) p[done + tid] = 0u;
+}
+
+// Enqueue the clear of `bytes` bytes (a multiple of 4) at p (4-byte aligned) on s.
+static inline int zero_fill_async(void *p, size_t bytes, hipStream_t s)
+{
+    if (bytes == 0) return FN2_OK;
+    if (bytes % 4 != 0 || !aligned(p, 4)) return FN2_EALIGN;
+    const size_t n = bytes / 4, want = (n / 4 + 255) / 256 + 1;
+    hipLaunchKernelGGL(zero_fill_kernel<0>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, static_cast<unsigned *>(p), n);
+    return launch_status();
+}
+
 static inline size_t dtype_size(int dtype)
 {
     switch (dtype) {

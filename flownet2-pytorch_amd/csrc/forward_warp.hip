@@ -300,8 +300,8 @@ size_t splat_det_workspace_bytes(const SplatP &p)
 int splat_forward(const float *in, const float *flow, float *out, const SplatP &p, bool tiled, hipStream_t s)
 {
     const size_t bytes = sizeof(float) * (size_t)p.B * p.C * p.H * p.W;
-    hipError_t e = hipMemsetAsync(out, 0, bytes, s);
-    if (e != hipSuccess) return (int)e;
+    int rc = zero_fill_async(out, bytes, s);
+    if (rc != FN2_OK) return rc;
     if (tiled)
         hipLaunchKernelGGL(splat_fwd_tiled, dim3((unsigned)p.B * p.tiles_x * p.tiles_y * p.group_runs), dim3(NT), 0, s, in, flow, out, p);
     else
@@ -313,14 +313,13 @@ int splat_forward(const float *in, const float *flow, float *out, const SplatP &
 int splat_forward_det(const float *in, const float *flow, float *out, void *workspace, const SplatP &p, hipStream_t s)
 {
     const long planes = (long)p.B * p.C, HW = (long)p.H * p.W;
-    hipError_t e = hipMemsetAsync(workspace, 0, splat_det_workspace_bytes(p), s);
-    if (e != hipSuccess) return (int)e;
+    int rc = zero_fill_async(workspace, splat_det_workspace_bytes(p), s);
+    if (rc != FN2_OK) return rc;
     unsigned *pmax = static_cast<unsigned *>(workspace);
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + (4 * planes + 255) / 256 * 256);
     const long cpp = (HW + NT * MAX_PER - 1) / (NT * MAX_PER);
     hipLaunchKernelGGL(splat_plane_max, dim3(capped((unsigned long long)planes * cpp)), dim3(NT), 0, s, in, pmax, HW, cpp, planes * cpp);
-    int rc = launch_status();
-    if (rc != FN2_OK) return rc;
+    if ((rc = launch_status()) != FN2_OK) return rc;
     hipLaunchKernelGGL(splat_fwd_general<true>, dim3((unsigned)p.B * p.chunks), dim3(NT), 0, s, in, flow, (float *)nullptr, acc, pmax, p);
     if ((rc = launch_status()) != FN2_OK) return rc;
     hipLaunchKernelGGL(splat_convert, dim3(capped(((unsigned long long)planes * HW + NT - 1) / NT)), dim3(NT), 0, s, acc, pmax, out, HW,

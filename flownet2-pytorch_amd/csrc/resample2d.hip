@@ -1889,8 +1889,8 @@ template <int MODE>
 static int det_begin(const DetSrc &d, int B, void *workspace, size_t bytes, DetAcc &det, int K, hipStream_t s)
 {
     const long planes = (long)B * d.C;
-    hipError_t e = hipMemsetAsync(workspace, 0, bytes, s);
-    if (e != hipSuccess) return (int)e;
+    const int rc = zero_fill_async(workspace, bytes, s);
+    if (rc != FN2_OK) return rc;
     det.pmax = static_cast<unsigned *>(workspace);
     det.acc = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + (4 * planes + 255) / 256 * 256);
     det.K = K;

@@ -9,7 +9,8 @@
 5. AlternateCorrBlock against RAFT's pooled all-pairs composition in float64, channel and level order pinned by a one-pixel fmap2;
 6. coords.requires_grad, a second backward and deterministic mode raise (warn_only: warns);
 7. forward + backward allocate the output and the two gradients, nothing of the all-pairs volume's size;
-8. the forward is not slower than the composition's;  9. AUTO is the kernel the header names.
+8. the forward is not slower than the composition's;  9. AUTO is the kernel the header names;
+10. forward + backward captured into a hipGraph: every replay clears grad_fmap2 before the scatter.
 
 Every output is pre-filled with NaN (an unwritten element shows) and sits inside a larger allocation filled with a sentinel that
 must be untouched afterwards.  Feature maps are the finite families of corr_contract_ref.family_inputs.
@@ -393,6 +394,54 @@ def test_coords_gradient_second_backward_and_deterministic_mode(dev):
     finally:
         torch.use_deterministic_algorithms(False)
     assert torch.equal(got[0], want[0]) and torch.allclose(got[1], want[1], rtol=1e-4, atol=1e-5)
+
+
+# ------------------------------------------------------------------ 10: hipGraph replay of the backward
+def test_backward_replays_from_a_hip_graph(dev):
+    """grad_fmap2 is a scatter of float atomics into a tensor the library clears on the stream first; captured into a hipGraph
+    that clear has to run on EVERY replay.  The module's forward and backward are captured once and replayed on three sets of
+    values in the captured buffers, the captured gradients poisoned with NaN before each replay: grad_fmap1 has the eager
+    call's bits, grad_fmap2 lies inside its any-order bound and is exactly zero where no term arrives."""
+    from networks.correlation_package import CorrLookup
+    r, C, s1, s2 = 3, 5, (13, 19), (6, 9)
+    B, (H, W), (H2, W2) = 2, s1, s2
+    scale = float(C) ** -0.5
+
+    def values(seed):
+        f1, f2 = _features(1, C, s1, s2, seed=seed)
+        return f1, f2, _coords("a", B, H, W, H2, W2, r, seed=seed + 2), R.grad_output("normal", (B, (2 * r + 1) ** 2, H, W), seed=seed + 3)
+
+    f1, f2, co, go = (t.to(dev) for t in values(50))
+    a, b = f1.requires_grad_(True), f2.requires_grad_(True)
+    layer = CorrLookup(r)
+
+    def step():
+        return torch.autograd.grad(layer(a, b, co), (a, b), go)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        g1, g2 = step()
+    for seed in (60, 70, 80):
+        fresh = values(seed)
+        with torch.no_grad():
+            for dst, src in zip((a, b, co, go), fresh):
+                dst.copy_(src)
+            g1.fill_(float("nan"))
+            g2.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        e1, _ = _bwd(a.detach(), b.detach(), co, go, r, scale, AUTO, what=f"eager backward, seed {seed}")
+        _same_bits(g1, e1, f"grad_fmap1 replayed, seed {seed}")
+        _, (x2, S2, n2) = RL.backward(*(t.numpy() for t in fresh), r, scale)
+        _within(g2, x2, RL.delta_grad2(x2, S2, n2, scale), f"grad_fmap2 replayed, seed {seed}")
+        assert bool((g2.cpu()[torch.from_numpy(n2 == 0)] == 0).all())
 
 
 # ------------------------------------------------------------------ 7: memory

@@ -307,6 +307,49 @@ def test_backward_within_the_bounds(dev, shape, family):
     _same_bits(only_f, gf, "grad_flow alone differs from the full call")
 
 
+
+# ------------------------------------------------------------------ 9. hipGraph replay
+@pytest.mark.parametrize("det", [False, True], ids=["atomic", "deterministic"])
+def test_forward_replays_from_a_hip_graph(dev, det):
+    """The forward adds into its output (the deterministic one into its workspace), so the clear the entry point enqueues is
+    part of the result: captured into a hipGraph it has to clear on EVERY replay.  The module's forward is captured once and
+    replayed on three inputs in the captured buffers, the captured output poisoned with NaN before each replay; a clear that
+    does not run leaves the NaN (or, in the workspace, the last replay's sums).  Atomic path: inside the forward bound;
+    deterministic path: the bits of the fixed-point contract."""
+    from networks.splat_package import ForwardWarp
+    shape = (2, 3, 17, 67)
+    cases = [_case(shape, f) for f in ("smooth", "random", "converge")]
+    x, fl = _dev(cases[0], dev, "inp", "flow")
+    layer = ForwardWarp()
+    try:
+        torch.use_deterministic_algorithms(det)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(3):
+                layer(x, fl)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph), torch.no_grad():
+            out = layer(x, fl)
+    finally:
+        torch.use_deterministic_algorithms(False)
+    for c in cases[1:] + cases[:1]:
+        nx, nfl = _dev(c, dev, "inp", "flow")
+        x.copy_(nx)
+        fl.copy_(nfl)
+        out.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert not torch.isnan(out).any(), "the replay left the poison: the output was not cleared"
+        if det:
+            _same_bits(out, c["fixed"], "deterministic forward replayed from a hipGraph")
+        else:
+            _within(out, c["out"], c["bound"], ("forward", "graph"), "forward replayed from a hipGraph")
+        empty = torch.from_numpy(c["S"] == 0).to(dev)
+        assert bool((_bits(out)[empty] == 0).all()), "replayed from a hipGraph: a cell without contributions is not +0"
+
 # ------------------------------------------------------------------ 6. autograd and modules
 def test_autograd_is_the_raw_calls(dev):
     from networks.splat_package import ForwardWarp, ForwardWarpFunction

@@ -247,3 +247,40 @@ def test_flownet2_layers_repeat_bitwise():
         r1, r2 = once(), once()
     for i, (x, y) in enumerate(zip(r1, r2)):
         assert_bits(x, y, f"result {i}")
+
+
+def test_backward_replays_from_a_hip_graph():
+    """The deterministic backward sums in an int64 workspace that the entry point clears on the stream; captured into a hipGraph
+    that clear has to run on EVERY replay (a workspace left as it was adds the last replay's sums).  Resample2d's forward and
+    backward are captured once under the flag and replayed on three sets of values in the captured buffers: the bits of the
+    eager deterministic call."""
+    from networks.resample2d_package.resample2d import Resample2d
+    img, flow, gout = case(2, 3, 40, 72, 40, 72, "bench", seed=20)
+    img.requires_grad_(True)
+    flow.requires_grad_(True)
+    layer = Resample2d()
+
+    def step():
+        return torch.autograd.grad(layer(img, flow), (img, flow), gout)
+
+    with deterministic():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            g1, g2 = step()
+        for kind, seed in (("translate", 21), ("sink", 22), ("bench", 23)):
+            fresh = case(2, 3, 40, 72, 40, 72, kind, seed=seed)
+            with torch.no_grad():
+                for dst, src in zip((img, flow, gout), fresh):
+                    dst.copy_(src)
+            graph.replay()
+            torch.cuda.synchronize()
+            e1, e2 = run_backward(*fresh)
+            assert_bits(g1, e1, f"grad_input1 replayed, {kind}")
+            assert_bits(g2, e2, f"grad_flow replayed, {kind}")
