@@ -1,11 +1,7 @@
-"""Builds libflownet2_hip.so (hand-written gfx950 HIP kernels + C ABI) and the three pybind
-modules correlation_cuda / resample2d_cuda / channelnorm_cuda, in-tree, without hipify; and libflownet2_hip_ext.so
-(include/flownet2_hip_ext.h: layers outside the drop-in boundary, Correlation1d) with its module correlation1d_cuda; and
-libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h: CorrLookup, RAFT's correlation lookup) with its module corr_lookup_cuda; and
-libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h: ConvexUpsample, RAFT's convex flow upsampling) with its module
-convex_upsample_cuda; and libflownet2_hip_splat.so (include/flownet2_hip_splat.h: ForwardWarp, forward flow splatting) with its module
-forward_warp_cuda; and libflownet2_hip_census.so (include/flownet2_hip_census.h: the ternary census distance) with its module census_cuda;
-and libflownet2_hip_smooth.so (include/flownet2_hip_smooth.h: the edge-aware smoothness term) with its module smoothness_cuda.
+"""Builds the HIP libraries and the pybind modules of this package, in-tree, without hipify.  LIBRARIES below is the one
+description of what there is: per library its sources, its public header under include/, its version script and the pybind
+modules that link it.  libflownet2_hip.so (hand-written gfx950 kernels + C ABI) is the drop-in boundary; every other library is
+a sibling of its own, self-contained, and none links another.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -14,6 +10,7 @@ hipcc cross-compiles for gfx950 without a GPU.  The pybind modules are plain C++
 the ATen headers; they never see a kernel and are not run through torch's hipify pass.
 """
 import argparse
+import collections
 import os
 import subprocess
 import sys
@@ -22,26 +19,38 @@ import sysconfig
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-LIB = os.path.join(LIBDIR, "libflownet2_hip.so")
+INCLUDE = os.path.join(HERE, "..", "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNEL_SRCS = ["capi.hip", "channelnorm.hip", "resample2d.hip", "resample2d_lowp.hip", "correlation_direct.hip", "correlation_dense.hip", "correlation_mfma.hip", "correlation_f16x2.hip", "correlation_f16x2_wide.hip", "correlation_f16_fwd.hip", "correlation_f16_bwd.hip", "correlation_f16x2_bwd.hip", "correlation_fused_bwd.hip", "correlation_f16x2_bwd_wide.hip", "correlation_mfma_bwd.hip", "correlation_mfma_f64.hip",
-               "multiscale_loss.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              "-munsafe-fp-atomics", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
-# libflownet2_hip_ext.so: a sibling library of its own (csrc/exports_ext.map), self-contained -- it does not link libflownet2_hip.so
-EXT_LIB = os.path.join(LIBDIR, "libflownet2_hip_ext.so")
-EXT_SRCS = ["capi_ext.hip", "correlation_1d.hip"]
-# sibling libraries by name: libflownet2_hip_<name>.so from its sources, csrc/exports_<name>.map and include/flownet2_hip_<name>.h;
-# the same flags, objects under lib/<name>/, and none links another
-SIBLINGS = {"ext": EXT_SRCS, "lookup": ["capi_lookup.hip", "corr_lookup.hip"],
-            "upsample": ["capi_upsample.hip", "convex_upsample.hip"], "splat": ["capi_splat.hip", "forward_warp.hip"],
-            "census": ["capi_census.hip", "census.hip"], "smooth": ["capi_smooth.hip", "smooth.hip"]}
-MODULES = ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda", "correlation1d_cuda", "corr_lookup_cuda",
-           "convex_upsample_cuda", "forward_warp_cuda", "census_cuda", "smoothness_cuda"]
-MODULE_LIBS = {"correlation1d_cuda": "flownet2_hip_ext", "corr_lookup_cuda": "flownet2_hip_lookup",
-               "convex_upsample_cuda": "flownet2_hip_upsample", "forward_warp_cuda": "flownet2_hip_splat",
-               "census_cuda": "flownet2_hip_census", "smoothness_cuda": "flownet2_hip_smooth"}   # every other module links libflownet2_hip.so
 MAX_JOBS = 16
+
+# One entry per library: lib<link>.so = libflownet2_hip[_<name>].so from `srcs` (csrc/), the same flags for all, its objects under
+# lib/<name>/; `header` (include/) is its public C ABI, `vmap` (csrc/) its version script, `modules` the pybind modules
+# (csrc/binding/) that link it -- each module links exactly one.  "" is the main library; its debug twin (build_lib(debug=True))
+# has no entry of its own.
+Library = collections.namedtuple("Library", "name link srcs header vmap modules")
+
+
+def _library(name, srcs, modules):
+    suffix = "_" + name if name else ""
+    return Library(name, "flownet2_hip" + suffix, srcs, "flownet2_hip%s.h" % suffix, "exports%s.map" % suffix, modules)
+
+
+LIBRARIES = {lib.name: lib for lib in (
+    _library("", ["capi.hip", "channelnorm.hip", "resample2d.hip", "resample2d_lowp.hip", "correlation_direct.hip", "correlation_dense.hip",
+                  "correlation_mfma.hip", "correlation_f16x2.hip", "correlation_f16x2_wide.hip", "correlation_f16_fwd.hip",
+                  "correlation_f16_bwd.hip", "correlation_f16x2_bwd.hip", "correlation_fused_bwd.hip", "correlation_f16x2_bwd_wide.hip",
+                  "correlation_mfma_bwd.hip", "correlation_mfma_f64.hip", "multiscale_loss.hip"],
+             ["correlation_cuda", "resample2d_cuda", "channelnorm_cuda", "multiscale_loss_cuda"]),
+    _library("ext", ["capi_ext.hip", "correlation_1d.hip"], ["correlation1d_cuda"]),     # layers outside the drop-in boundary
+    _library("lookup", ["capi_lookup.hip", "corr_lookup.hip"], ["corr_lookup_cuda"]),
+    _library("upsample", ["capi_upsample.hip", "convex_upsample.hip"], ["convex_upsample_cuda"]),
+    _library("splat", ["capi_splat.hip", "forward_warp.hip"], ["forward_warp_cuda"]),
+    _library("census", ["capi_census.hip", "census.hip"], ["census_cuda"]),
+    _library("smooth", ["capi_smooth.hip", "smooth.hip"], ["smoothness_cuda"]),
+)}
+MODULES = [m for lib in LIBRARIES.values() for m in lib.modules]
 
 
 def _newer(target, deps):
@@ -62,19 +71,18 @@ def _run(cmd):
 def build_lib(force=False, debug=False, ext=False):
     """libflownet2_hip.so (the product: public C ABI only) or, with debug=True, libflownet2_hip_debug.so: the same kernels plus
     the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs);
-    with ext=NAME the sibling library libflownet2_hip_NAME.so (SIBLINGS[NAME], the same flags, its own version script);
+    with ext=NAME the sibling library libflownet2_hip_NAME.so (LIBRARIES[NAME], the same flags, its own version script);
     ext=True means "ext"."""
-    ext = "ext" if ext is True else ext
-    objdir = os.path.join(LIBDIR, ext) if ext else os.path.join(LIBDIR, "debug") if debug else LIBDIR
-    lib = os.path.join(LIBDIR, "libflownet2_hip_%s.so" % ext) if ext else os.path.join(LIBDIR, "libflownet2_hip_debug.so") if debug else LIB
-    vmap = os.path.join(CSRC, "exports_%s.map" % ext if ext else "exports.map")
+    desc = LIBRARIES["ext" if ext is True else ext or ""]
+    twin = debug and not desc.name
+    objdir = os.path.join(LIBDIR, "debug" if twin else desc.name) if twin or desc.name else LIBDIR
+    lib = os.path.join(LIBDIR, "lib%s.so" % (desc.link + "_debug" if twin else desc.link))
+    vmap = os.path.join(CSRC, desc.vmap)
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip.h"))
-    if ext:
-        hdrs.append(os.path.join(HERE, "..", "include", "flownet2_hip_%s.h" % ext))
+    hdrs += [os.path.join(INCLUDE, h) for h in dict.fromkeys(("flownet2_hip.h", desc.header))]
     objs, jobs = [], []
-    for src in (SIBLINGS[ext] if ext else KERNEL_SRCS):
+    for src in desc.srcs:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         if force or not _newer(o, [s] + hdrs):
@@ -95,26 +103,24 @@ def build_modules(force=False):
     tinc = [os.path.join(tdir, "include"), os.path.join(tdir, "include", "torch", "csrc", "api", "include")]
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
+    shared = [os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(CSRC, "binding", "binding_status.h"),
+              os.path.join(INCLUDE, "flownet2_hip.h")]   # (the sibling headers take their codes and dtype enums from flownet2_hip.h)
     outs, jobs = [], []
-    for m in MODULES:
+    for lib, m in ((lib, m) for lib in LIBRARIES.values() for m in lib.modules):
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
-        deps = [src, os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(HERE, "..", "include", "flownet2_hip.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_ext.h"), os.path.join(HERE, "..", "include", "flownet2_hip_lookup.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_upsample.h"), os.path.join(HERE, "..", "include", "flownet2_hip_splat.h"),
-                os.path.join(HERE, "..", "include", "flownet2_hip_census.h"), os.path.join(HERE, "..", "include", "flownet2_hip_smooth.h")]
-        if force or not _newer(out, deps):
+        if force or not _newer(out, [src] + shared + [os.path.join(INCLUDE, lib.header)]):
             cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                    "-DTORCH_EXTENSION_NAME=" + m, "-DTORCH_API_INCLUDE_EXTENSION_H",
-                   "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi, "-I" + os.path.join(HERE, "..", "include"),
+                   "-D_GLIBCXX_USE_CXX11_ABI=%d" % abi, "-I" + INCLUDE,
                    "-I/opt/rocm/include", "-I" + sysconfig.get_paths()["include"]]
             cmd += ["-I" + i for i in tinc]
             cmd += [src, "-o", out, "-L" + os.path.join(tdir, "lib"), "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu",
-                    "-ltorch_hip", "-ltorch_python", "-L" + LIBDIR, "-l" + MODULE_LIBS.get(m, "flownet2_hip"),
+                    "-ltorch_hip", "-ltorch_python", "-L" + LIBDIR, "-l" + lib.link,
                     "-Wl,-rpath,$ORIGIN/lib", "-Wl,-rpath," + os.path.join(tdir, "lib")]
             jobs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         outs.append(out)
-    for cmd, pr in jobs:  # the three translation units compile concurrently
+    for cmd, pr in jobs:  # the modules' translation units compile concurrently
         log, _ = pr.communicate()
         if pr.returncode != 0:
             sys.stderr.write(" ".join(cmd) + "\n" + log)
@@ -131,7 +137,7 @@ def main():
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=8) as pool:
-        futs = [pool.submit(build_lib, a.force, False)] + [pool.submit(build_lib, a.force, ext=name) for name in SIBLINGS]
+        futs = [pool.submit(build_lib, a.force, ext=name) for name in LIBRARIES]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))
         for f in futs:

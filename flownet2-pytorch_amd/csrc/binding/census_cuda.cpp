@@ -8,24 +8,12 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the census header, spelled out here
-static void check_rcc(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape or parameter"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported size (a plane of 2^31 elements or more, or too many planes)"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_census: ", msg, " (code ", rc, ")");
-}
+// the status text of libflownet2_hip_census.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rcc(int rc, const char *op) { check_status(STATUS_CENSUS, rc, op); }
 
 struct Geo {
     int N, C, H, W;
 };
-
-static void check_f32(const at::Tensor &t, const char *op, const char *name)
-{
-    TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be float32, got ", t.scalar_type(), ": convert it with .float()");
-}
 
 // the arguments first, then where the tensors live: a wrong shape, dtype or parameter is reported as such on any device
 static Geo check_inputs(const at::Tensor &im1, const at::Tensor &im2, int64_t md, double scale, const char *op)
@@ -84,7 +72,7 @@ at::Tensor census_forward_alloc(at::Tensor &im1, at::Tensor &im2, int64_t md, do
 {
     check_inputs(im1, im2, md, scale, "census_cuda.forward_alloc");
     c10::DeviceGuard guard(im1.device());
-    at::Tensor output = at::empty({0}, im1.options());
+    at::Tensor output = unsized(im1);
     census_forward_hip(im1, im2, output, md, scale, normalize);
     return output;
 }
@@ -96,15 +84,12 @@ std::vector<at::Tensor> census_backward_alloc(at::Tensor &im1, at::Tensor &im2, 
     TORCH_CHECK(want1 || want2, "census_cuda.backward_alloc: neither gradient is wanted");
     check_inputs(im1, im2, md, scale, "census_cuda.backward_alloc");
     c10::DeviceGuard guard(im1.device());
-    at::Tensor g1 = want1 ? at::empty({0}, im1.options()) : at::Tensor(), g2 = want2 ? at::empty({0}, im1.options()) : at::Tensor();
+    at::Tensor g1 = want1 ? unsized(im1) : at::Tensor(), g2 = want2 ? unsized(im1) : at::Tensor();
     census_backward_hip(im1, im2, gradOutput, g1, g2, md, scale, normalize, want1, want2);
     return {g1, g2};
 }
 
 // ---- autograd node on the C++ side, as forward_warp_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct CensusOp : public torch::autograd::Function<CensusOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &im1, const at::Tensor &im2, int64_t md, double scale, bool normalize)
     {
@@ -118,9 +103,7 @@ struct CensusOp : public torch::autograd::Function<CensusOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "CensusFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "CensusFunction.backward");
         auto saved = ctx->get_saved_variables();
         at::Tensor a = saved[0], b = saved[1], go = grad_outputs[0];
         const bool w1 = ctx->needs_input_grad(0), w2 = ctx->needs_input_grad(1);

@@ -73,9 +73,6 @@ at::Tensor channelnorm_backward_alloc(at::Tensor &input1, at::Tensor &output, at
 }
 
 // ---- autograd Function on the C++ side; semantics of networks/channelnorm_package/channelnorm.py
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct ChannelNormOp : public torch::autograd::Function<ChannelNormOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &input1, int64_t norm_deg)
     {

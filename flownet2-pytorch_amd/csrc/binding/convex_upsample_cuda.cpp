@@ -8,16 +8,8 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the upsample header, spelled out here
-static void check_rcu(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape or parameter (factor must be 2, 4 or 8)"
-                      : rc == FN2_EDTYPE ? "dtype not supported by this op (mask: float32, float16 or bfloat16)"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported size (at most 4 flow channels)"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_upsample: ", msg, " (code ", rc, ")");
-}
+// the status text of libflownet2_hip_upsample.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rcu(int rc, const char *op) { check_status(STATUS_UPSAMPLE, rc, op); }
 
 struct Geo {
     int B, C, H, W, dtype;
@@ -87,7 +79,7 @@ at::Tensor convex_upsample_forward_alloc(at::Tensor &flow, at::Tensor &mask, int
 {
     check_inputs(flow, mask, factor, "convex_upsample_cuda.forward_alloc");
     c10::DeviceGuard guard(flow.device());
-    at::Tensor output = at::empty({0}, flow.options());
+    at::Tensor output = unsized(flow);
     convex_upsample_forward_hip(flow, mask, output, factor, scale);
     return output;
 }
@@ -96,15 +88,12 @@ std::vector<at::Tensor> convex_upsample_backward_alloc(at::Tensor &flow, at::Ten
 {
     check_inputs(flow, mask, factor, "convex_upsample_cuda.backward_alloc");
     c10::DeviceGuard guard(flow.device());
-    at::Tensor gf = at::empty({0}, flow.options()), gm = at::empty({0}, mask.options());
+    at::Tensor gf = unsized(flow), gm = unsized(mask);
     convex_upsample_backward_hip(flow, mask, gradOutput, gf, gm, factor, scale);
     return {gf, gm};
 }
 
 // ---- autograd node on the C++ side, as corr_lookup_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct ConvexUpsampleOp : public torch::autograd::Function<ConvexUpsampleOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &flow, const at::Tensor &mask, int64_t factor, double scale)
     {
@@ -117,9 +106,7 @@ struct ConvexUpsampleOp : public torch::autograd::Function<ConvexUpsampleOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "ConvexUpsampleFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "ConvexUpsampleFunction.backward");
         auto saved = ctx->get_saved_variables();
         at::Tensor a = saved[0], m = saved[1], go = grad_outputs[0];
         auto g = convex_upsample_backward_alloc(a, m, go, (int)ctx->saved_data["factor"].toInt(), ctx->saved_data["scale"].toDouble());

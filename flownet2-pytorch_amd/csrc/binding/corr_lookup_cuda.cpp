@@ -7,16 +7,8 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the lookup header, spelled out here
-static void check_rcl(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape or parameter (radius must be 0 .. 8)"
-                      : rc == FN2_EDTYPE ? "dtype not supported by this op (float32 only)"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported size or selector"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_lookup: ", msg, " (code ", rc, ")");
-}
+// the status text of libflownet2_hip_lookup.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rcl(int rc, const char *op) { check_status(STATUS_LOOKUP, rc, op); }
 
 struct Geo {
     int B, C, H, W, H2, W2;
@@ -67,7 +59,7 @@ int corr_lookup_backward_hip(at::Tensor &fmap1, at::Tensor &fmap2, at::Tensor &c
                     gradOutput.size(3) == g.W,
                 op, ": gradOutput has shape ", gradOutput.sizes(), ", expected [", g.B, ", ", D * D, ", ", g.H, ", ", g.W, "]");
     // grad_fmap2 is summed by float atomics in arrival order
-    if (at::globalContext().deterministicAlgorithms()) at::globalContext().alertNotDeterministic("corr_lookup_cuda.backward");
+    if (deterministic()) at::globalContext().alertNotDeterministic("corr_lookup_cuda.backward");
     c10::DeviceGuard guard(fmap1.device());
     at::Tensor a = fmap1.contiguous(), b = fmap2.contiguous(), c = coords.contiguous(), go = gradOutput.contiguous();
     gradFmap1.resize_({g.B, g.C, g.H, g.W});     // fully written, no fill_(0); grad_fmap2 is cleared by the library on the stream
@@ -83,7 +75,7 @@ at::Tensor corr_lookup_forward_alloc(at::Tensor &fmap1, at::Tensor &fmap2, at::T
 {
     check_gpu(fmap1, "corr_lookup_cuda.forward_alloc", "fmap1");
     c10::DeviceGuard guard(fmap1.device());
-    at::Tensor output = at::empty({0}, fmap1.options());
+    at::Tensor output = unsized(fmap1);
     corr_lookup_forward_hip(fmap1, fmap2, coords, output, radius, scale);
     return output;
 }
@@ -93,15 +85,12 @@ std::vector<at::Tensor> corr_lookup_backward_alloc(at::Tensor &fmap1, at::Tensor
 {
     check_gpu(fmap1, "corr_lookup_cuda.backward_alloc", "fmap1");
     c10::DeviceGuard guard(fmap1.device());
-    at::Tensor g1 = at::empty({0}, fmap1.options()), g2 = at::empty({0}, fmap1.options());
+    at::Tensor g1 = unsized(fmap1), g2 = unsized(fmap1);
     corr_lookup_backward_hip(fmap1, fmap2, coords, gradOutput, g1, g2, radius, scale);
     return {g1, g2};
 }
 
 // ---- autograd node on the C++ side, as correlation1d_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct CorrLookupOp : public torch::autograd::Function<CorrLookupOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &fmap1, const at::Tensor &fmap2, const at::Tensor &coords,
                               int64_t radius, double scale)
@@ -115,9 +104,7 @@ struct CorrLookupOp : public torch::autograd::Function<CorrLookupOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "CorrLookupFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "CorrLookupFunction.backward");
         auto saved = ctx->get_saved_variables();
         at::Tensor a = saved[0], b = saved[1], c = saved[2], go = grad_outputs[0];
         auto g = corr_lookup_backward_alloc(a, b, c, go, (int)ctx->saved_data["radius"].toInt(), ctx->saved_data["scale"].toDouble());

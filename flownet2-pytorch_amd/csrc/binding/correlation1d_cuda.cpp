@@ -7,31 +7,16 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the ext header, spelled out here
-static void check_rc1d(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape or parameter"
-                      : rc == FN2_EDTYPE ? "dtype not supported by this op"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported parameter combination (the backward needs stride1 == 1)"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_ext: ", msg, " (code ", rc, ")");
-}
+// the status text of libflownet2_hip_ext.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rc1d(int rc, const char *op) { check_status(STATUS_EXT, rc, op); }
 
 int correlation1d_forward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &output, int pad_size, int max_displacement,
                               int stride1, int stride2, int single_direction)
 {
     const char *op = "correlation1d_cuda.forward";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, output, op, "output");
-    TORCH_CHECK(input1.dim() == 4 && input2.dim() == 4, op, ": inputs must be 4-D (N, C, H, W)");
-    TORCH_CHECK(input1.sizes() == input2.sizes(), op, ": input1 ", input1.sizes(), " and input2 ", input2.sizes(),
-                " must have the same shape");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc1d(fn2x_correlation1d_output_shape(H, W, pad_size, max_displacement, stride1, stride2, single_direction, &nOut, &oH, &oW), op);
+    PairGeo g = check_pair(input1, input2, {{output, "output"}}, op, true);
+    check_rc1d(fn2x_correlation1d_output_shape(g.H, g.W, pad_size, max_displacement, stride1, stride2, single_direction, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
     c10::DeviceGuard guard(input1.device());
     at::Tensor a = input1.contiguous(), b = input2.contiguous();
     output.resize_({B, nOut, oH, oW});   // fully written by the kernel, no fill_(0)
@@ -46,19 +31,10 @@ int correlation1d_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tenso
                                int single_direction)
 {
     const char *op = "correlation1d_cuda.backward";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, gradOutput, op, "gradOutput");
-    check_same(input1, gradInput1, op, "gradInput1");
-    check_same(input1, gradInput2, op, "gradInput2");
-    TORCH_CHECK(input1.dim() == 4 && input1.sizes() == input2.sizes(), op, ": inputs must be 4-D and equally shaped");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc1d(fn2x_correlation1d_output_shape(H, W, pad_size, max_displacement, stride1, stride2, single_direction, &nOut, &oH, &oW), op);
-    TORCH_CHECK(gradOutput.dim() == 4 && gradOutput.size(0) == B && gradOutput.size(1) == nOut && gradOutput.size(2) == oH &&
-                    gradOutput.size(3) == oW,
-                op, ": gradOutput has shape ", gradOutput.sizes(), ", expected [", B, ", ", nOut, ", ", oH, ", ", oW, "]");
+    PairGeo g = check_pair(input1, input2, {{gradOutput, "gradOutput"}, {gradInput1, "gradInput1"}, {gradInput2, "gradInput2"}}, op);
+    check_rc1d(fn2x_correlation1d_output_shape(g.H, g.W, pad_size, max_displacement, stride1, stride2, single_direction, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
+    check_grad_output(gradOutput, g, op);
     c10::DeviceGuard guard(input1.device());
     at::Tensor a = input1.contiguous(), b = input2.contiguous(), go = gradOutput.contiguous();
     gradInput1.resize_({B, C, H, W});   // fully written, no fill_(0)
@@ -75,7 +51,7 @@ at::Tensor correlation1d_forward_alloc(at::Tensor &input1, at::Tensor &input2, i
 {
     check_gpu(input1, "correlation1d_cuda.forward_alloc", "input1");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor output = at::empty({0}, input1.options());
+    at::Tensor output = unsized(input1);
     correlation1d_forward_hip(input1, input2, output, pad_size, max_displacement, stride1, stride2, single_direction);
     return output;
 }
@@ -85,15 +61,12 @@ std::vector<at::Tensor> correlation1d_backward_alloc(at::Tensor &input1, at::Ten
 {
     check_gpu(input1, "correlation1d_cuda.backward_alloc", "input1");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor g1 = at::empty({0}, input1.options()), g2 = at::empty({0}, input1.options());
+    at::Tensor g1 = unsized(input1), g2 = unsized(input1);
     correlation1d_backward_hip(input1, input2, gradOutput, g1, g2, pad_size, max_displacement, stride1, stride2, single_direction);
     return {g1, g2};
 }
 
 // ---- autograd node on the C++ side, as correlation_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct Correlation1dOp : public torch::autograd::Function<Correlation1dOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &input1, const at::Tensor &input2, int64_t pad_size,
                               int64_t max_displacement, int64_t stride1, int64_t stride2, int64_t single_direction)
@@ -106,9 +79,7 @@ struct Correlation1dOp : public torch::autograd::Function<Correlation1dOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "Correlation1dFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "Correlation1dFunction.backward");
         auto saved = ctx->get_saved_variables();
         const auto p = ctx->saved_data["p"].toIntVector();
         at::Tensor a = saved[0], b = saved[1], go = grad_outputs[0];

@@ -1,6 +1,7 @@
 // correlation_cuda.cpp -- pybind module `correlation_cuda` (drop-in for the reference's module of
 // the same name, correlation_cuda.cc:10-172): forward / backward with the reference's positional
-// signature, tensors owned by Python, outputs resized in place.
+// signature, tensors owned by Python, outputs resized in place.  The checks of the input pair and of gradOutput's shape are
+// binding_common.h's check_pair / check_grad_output, shared with correlation1d_cuda.
 #include "binding_common.h"
 
 using namespace fn2b;
@@ -13,17 +14,9 @@ int correlation_forward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor &
 {
     (void)rInput1; (void)rInput2; (void)corr_type_multiply; // accepted, unused (as in the reference kernels)
     const char *op = "correlation_cuda.forward";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, output, op, "output");
-    TORCH_CHECK(input1.dim() == 4 && input2.dim() == 4, op, ": inputs must be 4-D (N, C, H, W)");
-    TORCH_CHECK(input1.sizes() == input2.sizes(), op, ": input1 ", input1.sizes(), " and input2 ", input2.sizes(),
-                " must have the same shape");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc(fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH,
-                                          &oW), op);
+    PairGeo g = check_pair(input1, input2, {{output, "output"}}, op, true);
+    check_rc(fn2_correlation_output_shape(g.H, g.W, pad_size, kernel_size, max_displacement, stride1, stride2, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
     c10::DeviceGuard guard(input1.device());
     at::Tensor a = input1.contiguous(), b = input2.contiguous();
     output.resize_({B, nOut, oH, oW}); // correlation_cuda.cc:38; fully written by the kernel, no fill_(0)
@@ -41,15 +34,9 @@ int correlation_forward_fused_hip(at::Tensor &input1, at::Tensor &input2, at::Te
                                   int stride2)
 {
     const char *op = "correlation_cuda.forward_fused";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, buffer, op, "buffer");
-    TORCH_CHECK(input1.dim() == 4 && input1.sizes() == input2.sizes(), op, ": inputs must be 4-D and equally shaped");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc(fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH,
-                                          &oW), op);
+    PairGeo g = check_pair(input1, input2, {{buffer, "buffer"}}, op);
+    check_rc(fn2_correlation_output_shape(g.H, g.W, pad_size, kernel_size, max_displacement, stride1, stride2, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
     TORCH_CHECK(buffer.dim() == 4 && buffer.is_contiguous() && buffer.size(0) == B && buffer.size(2) == oH &&
                     buffer.size(3) == oW && channel_offset >= 0 && channel_offset + nOut <= buffer.size(1),
                 op, ": buffer ", buffer.sizes(), " cannot hold ", nOut, " channels of ", oH, "x", oW, " at channel ",
@@ -99,20 +86,10 @@ int correlation_backward_hip(at::Tensor &input1, at::Tensor &input2, at::Tensor 
 {
     (void)rInput1; (void)rInput2; (void)corr_type_multiply;
     const char *op = "correlation_cuda.backward";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, gradOutput, op, "gradOutput");
-    check_same(input1, gradInput1, op, "gradInput1");
-    check_same(input1, gradInput2, op, "gradInput2");
-    TORCH_CHECK(input1.dim() == 4 && input1.sizes() == input2.sizes(), op, ": inputs must be 4-D and equally shaped");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc(fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH,
-                                          &oW), op);
-    TORCH_CHECK(gradOutput.dim() == 4 && gradOutput.size(0) == B && gradOutput.size(1) == nOut &&
-                    gradOutput.size(2) == oH && gradOutput.size(3) == oW,
-                op, ": gradOutput has shape ", gradOutput.sizes(), ", expected [", B, ", ", nOut, ", ", oH, ", ", oW, "]");
+    PairGeo g = check_pair(input1, input2, {{gradOutput, "gradOutput"}, {gradInput1, "gradInput1"}, {gradInput2, "gradInput2"}}, op);
+    check_rc(fn2_correlation_output_shape(g.H, g.W, pad_size, kernel_size, max_displacement, stride1, stride2, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
+    check_grad_output(gradOutput, g, op);
     c10::DeviceGuard guard(input1.device());
     at::Tensor a = input1.contiguous(), b = input2.contiguous();
     at::Tensor go = gradOutput.contiguous(); // the reference assumes contiguity without checking (SURVEY.md b)
@@ -136,18 +113,9 @@ int correlation_backward_fused_hip(at::Tensor &input1, at::Tensor &input2, at::T
                                    int pad_size, int kernel_size, int max_displacement, int stride1, int stride2)
 {
     const char *op = "correlation_cuda.backward_fused";
-    check_gpu(input1, op, "input1");
-    check_same(input1, input2, op, "input2");
-    check_same(input1, buffer, op, "buffer");
-    check_same(input1, gradBuffer, op, "gradBuffer");
-    check_same(input1, gradInput1, op, "gradInput1");
-    check_same(input1, gradInput2, op, "gradInput2");
-    TORCH_CHECK(input1.dim() == 4 && input1.sizes() == input2.sizes(), op, ": inputs must be 4-D and equally shaped");
-    const int dt = dtype_of(input1, op);
-    const int B = input1.size(0), C = input1.size(1), H = input1.size(2), W = input1.size(3);
-    int nOut = 0, oH = 0, oW = 0;
-    check_rc(fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH,
-                                          &oW), op);
+    PairGeo g = check_pair(input1, input2, {{buffer, "buffer"}, {gradBuffer, "gradBuffer"}, {gradInput1, "gradInput1"}, {gradInput2, "gradInput2"}}, op);
+    check_rc(fn2_correlation_output_shape(g.H, g.W, pad_size, kernel_size, max_displacement, stride1, stride2, &g.nOut, &g.oH, &g.oW), op);
+    const auto [dt, B, C, H, W, nOut, oH, oW] = g;
     TORCH_CHECK(buffer.dim() == 4 && buffer.is_contiguous() && buffer.size(0) == B && buffer.size(2) == oH &&
                     buffer.size(3) == oW && channel_offset >= 0 && channel_offset + nOut <= buffer.size(1),
                 op, ": buffer ", buffer.sizes(), " does not hold ", nOut, " channels of ", oH, "x", oW, " at channel ", channel_offset);
@@ -187,7 +155,7 @@ at::Tensor correlation_forward_alloc(at::Tensor &input1, at::Tensor &input2, int
 {
     check_gpu(input1, "correlation_cuda.forward_alloc", "input1");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor scratch1 = at::empty({0}, input1.options()), scratch2 = at::empty({0}, input1.options()), output = at::empty({0}, input1.options());
+    at::Tensor scratch1 = unsized(input1), scratch2 = unsized(input1), output = unsized(input1);
     correlation_forward_hip(input1, input2, scratch1, scratch2, output, pad_size, kernel_size, max_displacement, stride1, stride2, corr_type_multiply);
     return output;
 }
@@ -197,8 +165,7 @@ std::vector<at::Tensor> correlation_backward_alloc(at::Tensor &input1, at::Tenso
 {
     check_gpu(input1, "correlation_cuda.backward_alloc", "input1");
     c10::DeviceGuard guard(input1.device());
-    at::Tensor scratch1 = at::empty({0}, input1.options()), scratch2 = at::empty({0}, input1.options());
-    at::Tensor g1 = at::empty({0}, input1.options()), g2 = at::empty({0}, input1.options());
+    at::Tensor scratch1 = unsized(input1), scratch2 = unsized(input1), g1 = unsized(input1), g2 = unsized(input1);
     correlation_backward_hip(input1, input2, scratch1, scratch2, gradOutput, g1, g2, pad_size, kernel_size, max_displacement, stride1, stride2,
                              corr_type_multiply);
     return {g1, g2};
@@ -207,16 +174,6 @@ std::vector<at::Tensor> correlation_backward_alloc(at::Tensor &input1, at::Tenso
 // ---- autograd Functions on the C++ side: `Correlation` / `CorrelationLeakyReLUCat` do no Python between
 // `apply` and the launch, and the engine calls the backward without taking the GIL.  Same semantics as the Python Functions of
 // networks/correlation_package/correlation.py (kept there for code written against CorrelationFunction.forward / .backward).
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
-static void check_once_differentiable(const variable_list &grads, const char *op)
-{
-    for (const auto &g : grads)
-        TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), op,
-                    ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
-}
-
 struct CorrelationOp : public torch::autograd::Function<CorrelationOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &input1, const at::Tensor &input2, int64_t pad_size, int64_t kernel_size,
                               int64_t max_displacement, int64_t stride1, int64_t stride2, int64_t corr_multiply)
@@ -276,8 +233,8 @@ struct CorrelationLeakyReLUCatOp : public torch::autograd::Function<CorrelationL
         at::Tensor g1, g2, gr;
         if (ctx->needs_input_grad(0) || ctx->needs_input_grad(1)) {
             c10::DeviceGuard guard(a.device());
-            g1 = at::empty({0}, a.options());
-            g2 = at::empty({0}, a.options());
+            g1 = unsized(a);
+            g2 = unsized(a);
             correlation_backward_fused_hip(a, b, buf, gbuf, (int)p[5], slope, g1, g2, (int)p[0], (int)p[1], (int)p[2], (int)p[3], (int)p[4]);
         }
         if (ctx->needs_input_grad(2)) gr = gbuf.narrow(1, 0, p[5]);

@@ -9,31 +9,20 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the splat header, spelled out here
-static void check_rcs(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape, selector or workspace"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported size (a plane of 2^31 elements or more, or too many planes)"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_splat: ", msg, " (code ", rc, ")");
-}
-
-static bool deterministic() { return at::globalContext().deterministicAlgorithms(); }
-// straight from the caching allocator of the current device (at::empty would fill it under the deterministic flag; the entry
-// point clears it on the stream itself); released to the allocator when the DataPtr goes, as a temporary tensor is
-static c10::DataPtr det_workspace(size_t bytes) { return c10::GetAllocator(c10::DeviceType::CUDA)->allocate(bytes); }
+// the status text of libflownet2_hip_splat.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rcs(int rc, const char *op) { check_status(STATUS_SPLAT, rc, op); }
 
 struct Geo {
     int B, C, H, W;
 };
 
-static void check_f32(const at::Tensor &t, const char *op, const char *name)
+// binding_common.h's check_f32 behind a hint of this layer's own for half and bfloat16 tensors
+static void check_f32_not16(const at::Tensor &t, const char *op, const char *name)
 {
     const bool is16 = t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
     TORCH_CHECK(!is16, op, ": ", name, " must be float32, got ", t.scalar_type(),
                 ": call .float() on it (a 16-bit accumulating output would round at every add)");
-    TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be float32, got ", t.scalar_type(), ": convert it with .float()");
+    check_f32(t, op, name);
 }
 
 // the arguments first, then where the tensors live: a wrong shape or dtype is reported as such on any device
@@ -46,8 +35,8 @@ static Geo check_inputs(const at::Tensor &input, const at::Tensor &flow, const c
     TORCH_CHECK(flow.size(0) == input.size(0) && flow.size(2) == input.size(2) && flow.size(3) == input.size(3), op, ": flow ", flow.sizes(),
                 " must have the batch size, height and width of input ", input.sizes(),
                 " (the output has the input's size; resize the flow first)");
-    check_f32(input, op, "input");
-    check_f32(flow, op, "flow");
+    check_f32_not16(input, op, "input");
+    check_f32_not16(flow, op, "flow");
     check_gpu(input, op, "input");
     check_gpu(flow, op, "flow");
     TORCH_CHECK(flow.device() == input.device(), op, ": flow is on ", flow.device(), ", expected ", input.device());
@@ -102,7 +91,7 @@ at::Tensor forward_warp_forward_alloc(at::Tensor &input, at::Tensor &flow, int a
     TORCH_CHECK(algo >= FN2S_AUTO && algo <= FN2S_TILED, "forward_warp_cuda.forward_alloc: algo ", algo, " is not 0 (auto), 1 (general) or 2 (tiled)");
     check_inputs(input, flow, "forward_warp_cuda.forward_alloc");
     c10::DeviceGuard guard(input.device());
-    at::Tensor output = at::empty({0}, input.options());
+    at::Tensor output = unsized(input);
     forward_warp_forward_hip(input, flow, output, algo);
     return output;
 }
@@ -113,15 +102,12 @@ std::vector<at::Tensor> forward_warp_backward_alloc(at::Tensor &input, at::Tenso
     TORCH_CHECK(want_input || want_flow, "forward_warp_cuda.backward_alloc: neither gradient is wanted");
     check_inputs(input, flow, "forward_warp_cuda.backward_alloc");
     c10::DeviceGuard guard(input.device());
-    at::Tensor gi = want_input ? at::empty({0}, input.options()) : at::Tensor(), gf = want_flow ? at::empty({0}, input.options()) : at::Tensor();
+    at::Tensor gi = want_input ? unsized(input) : at::Tensor(), gf = want_flow ? unsized(input) : at::Tensor();
     forward_warp_backward_hip(input, flow, gradOutput, gi, gf, want_input, want_flow);
     return {gi, gf};
 }
 
 // ---- autograd node on the C++ side, as convex_upsample_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct ForwardWarpOp : public torch::autograd::Function<ForwardWarpOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &input, const at::Tensor &flow)
     {
@@ -132,9 +118,7 @@ struct ForwardWarpOp : public torch::autograd::Function<ForwardWarpOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "ForwardWarpFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "ForwardWarpFunction.backward");
         auto saved = ctx->get_saved_variables();
         at::Tensor a = saved[0], f = saved[1], go = grad_outputs[0];
         const bool wi = ctx->needs_input_grad(0), wf = ctx->needs_input_grad(1);

@@ -10,8 +10,6 @@
 #include <unordered_map>
 
 using namespace fn2b;
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
 
 namespace {
 

@@ -19,10 +19,7 @@ static bool widen_bf16(const at::Tensor &t, const char *op)
 
 // torch.use_deterministic_algorithms(True), warn_only included: the backward passes that scatter grad_input1 take the fixed-point entry
 // points (fn2_*_backward_det), whose results do not depend on the order of the additions; the workspace comes from the caching allocator
-static bool deterministic() { return at::globalContext().deterministicAlgorithms(); }
-// straight from the caching allocator of the current device (at::empty would fill it under the deterministic flag; the entry point clears
-// it on the stream itself); released to the allocator when the DataPtr goes, as a temporary tensor is
-static c10::DataPtr det_workspace(size_t bytes) { return c10::GetAllocator(c10::DeviceType::CUDA)->allocate(bytes); }
+// (deterministic() and det_workspace() of binding_common.h)
 
 // half / bfloat16: the element types the 16-bit entry points of the fused warp rows take
 static bool is_lowp(const at::Tensor &t) { return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16; }
@@ -278,16 +275,6 @@ std::vector<at::Tensor> resample2d_backward_alloc(at::Tensor &input1, at::Tensor
 
 // ---- autograd Functions on the C++ side: no Python between `apply` and the launch, no GIL in the backward.
 // Same semantics as the Python Functions of networks/resample2d_package/resample2d.py.
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
-static void check_once_differentiable(const variable_list &grads, const char *op)
-{
-    for (const auto &g : grads)
-        TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), op,
-                    ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
-}
-
 struct Resample2dOp : public torch::autograd::Function<Resample2dOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &input1, const at::Tensor &input2, int64_t kernel_size, bool bilinear)
     {
@@ -356,9 +343,9 @@ struct WarpDiffNormCatOp : public torch::autograd::Function<WarpDiffNormCatOp> {
         at::Tensor x = saved[0], flow = saved[1], out = saved.size() > 2 ? saved[2] : at::Tensor();
         c10::DeviceGuard guard(x.device());
         at::Tensor go = grad_outputs[0].to(x.scalar_type()).contiguous();   // (widened path: the 16-bit gradient widened, exact)
-        at::Tensor gx = need_x ? at::empty_like(x) : at::empty({0}, x.options());
+        at::Tensor gx = need_x ? at::empty_like(x) : unsized(x);
         at::Tensor gflow = at::empty_like(flow);
-        if (!out.defined()) out = at::empty({0}, x.options());
+        if (!out.defined()) out = unsized(x);
         warp_diff_norm_cat_backward_hip(x, flow, out, go, gx, gflow, ctx->saved_data["d"].toDouble(), ctx->saved_data["b"].toBool());
         const auto tx = (at::ScalarType)ctx->saved_data["tx"].toInt(), tf = (at::ScalarType)ctx->saved_data["tf"].toInt();
         return {need_x ? gx.to(tx) : at::Tensor(), need_flow ? gflow.to(tf) : at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
@@ -399,7 +386,7 @@ struct WarpDiffNormOp : public torch::autograd::Function<WarpDiffNormOp> {
         check_once_differentiable(grad_outputs, "WarpDiffNormFunction.backward");
         if (!ctx->needs_input_grad(1)) return {at::Tensor(), at::Tensor(), at::Tensor()};
         auto saved = ctx->get_saved_variables();
-        at::Tensor x = saved[0], flow = saved[1], norm = saved.size() > 2 ? saved[2] : at::empty({0}, saved[0].options());
+        at::Tensor x = saved[0], flow = saved[1], norm = saved.size() > 2 ? saved[2] : unsized(saved[0]);
         at::Tensor gn = grad_outputs[0].to(x.scalar_type());
         at::Tensor gflow = warp_diff_norm_backward_hip(x, flow, norm, gn, ctx->saved_data["b"].toBool());
         return {at::Tensor(), gflow.to((at::ScalarType)ctx->saved_data["tf"].toInt()), at::Tensor()};

@@ -8,24 +8,12 @@
 
 using namespace fn2b;
 
-// fn2_strerror lives in libflownet2_hip.so, which this module does not link: the codes of the smoothness header, spelled out here
-static void check_rcm(int rc, const char *op)
-{
-    const char *msg = rc == FN2_EINVAL ? "invalid shape or parameter"
-                      : rc == FN2_EALIGN ? "pointer not aligned to its element size"
-                      : rc == FN2_EUNSUPPORTED ? "unsupported size (a plane of 2^31 elements or more, or too many planes)"
-                      : rc > 0 ? "hipError_t from the launch" : "unknown error";
-    TORCH_CHECK(rc == FN2_OK, op, ": HIP call failed: flownet2_hip_smooth: ", msg, " (code ", rc, ")");
-}
+// the status text of libflownet2_hip_smooth.so (binding_status.h): this module does not link the library fn2_strerror lives in
+static void check_rcm(int rc, const char *op) { check_status(STATUS_SMOOTH, rc, op); }
 
 struct Geo {
     int N, F, C, H, W;
 };
-
-static void check_f32(const at::Tensor &t, const char *op, const char *name)
-{
-    TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be float32, got ", t.scalar_type(), ": convert it with .float()");
-}
 
 // the arguments first, then where the tensors live: a wrong shape, dtype or parameter is reported as such on any device
 static Geo check_inputs(const at::Tensor &flow, const at::Tensor &image, int64_t order, int64_t edge, double alpha, double eps, const char *op)
@@ -85,7 +73,7 @@ at::Tensor smoothness_forward_alloc(at::Tensor &flow, at::Tensor &image, int64_t
 {
     check_inputs(flow, image, order, edge, alpha, eps, "smoothness_cuda.forward_alloc");
     c10::DeviceGuard guard(flow.device());
-    at::Tensor output = at::empty({0}, flow.options());
+    at::Tensor output = unsized(flow);
     smoothness_forward_hip(flow, image, output, order, edge, alpha, eps);
     return output;
 }
@@ -100,9 +88,6 @@ at::Tensor smoothness_backward_alloc(at::Tensor &flow, at::Tensor &image, at::Te
 }
 
 // ---- autograd node on the C++ side, as census_cuda.apply: no Python between `apply` and the launch
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
 struct SmoothnessOp : public torch::autograd::Function<SmoothnessOp> {
     static at::Tensor forward(AutogradContext *ctx, const at::Tensor &flow, const at::Tensor &image, int64_t order, int64_t edge, double alpha,
                               double eps)
@@ -118,9 +103,7 @@ struct SmoothnessOp : public torch::autograd::Function<SmoothnessOp> {
 
     static variable_list backward(AutogradContext *ctx, variable_list grad_outputs)
     {
-        for (const auto &g : grad_outputs)
-            TORCH_CHECK(!(g.defined() && g.requires_grad() && at::GradMode::is_enabled()), "SmoothnessFunction.backward",
-                        ": the backward of this layer is a HIP kernel and not differentiable a second time (create_graph=True)");
+        check_once_differentiable(grad_outputs, "SmoothnessFunction.backward");
         auto saved = ctx->get_saved_variables();
         at::Tensor a = saved[0], b = saved[1], go = grad_outputs[0];
         if (!ctx->needs_input_grad(0)) return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};

@@ -43,167 +43,115 @@ EXT_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_ext.so")
 EXT_EXPORTS = ["fn2x_abi_version", "fn2x_correlation1d_output_shape", "fn2x_correlation1d_forward", "fn2x_correlation1d_backward"]
 FN2X_CORR1D_AUTO, FN2X_CORR1D_GENERAL, FN2X_CORR1D_TILED = 0, 1, 2
 
-# libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h): CorrLookup, RAFT's correlation lookup; the third library
+# libflownet2_hip_lookup.so (include/flownet2_hip_lookup.h): CorrLookup, RAFT's correlation lookup
 LOOKUP_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_lookup.so")
 LOOKUP_EXPORTS = ["fn2l_abi_version", "fn2l_corr_lookup_forward", "fn2l_corr_lookup_backward"]
 FN2L_LOOKUP_AUTO, FN2L_LOOKUP_GENERAL, FN2L_LOOKUP_STAGED = 0, 1, 2
 
-# libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h): ConvexUpsample, RAFT's convex flow upsampling; the fourth library
+# libflownet2_hip_upsample.so (include/flownet2_hip_upsample.h): ConvexUpsample, RAFT's convex flow upsampling
 UPSAMPLE_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_upsample.so")
 UPSAMPLE_EXPORTS = ["fn2u_abi_version", "fn2u_convex_upsample_forward", "fn2u_convex_upsample_backward",
                     "fn2u_convex_upsample_backward_workspace_bytes"]
 
-# libflownet2_hip_splat.so (include/flownet2_hip_splat.h): ForwardWarp, forward flow splatting; the fifth library
+# libflownet2_hip_splat.so (include/flownet2_hip_splat.h): ForwardWarp, forward flow splatting
 SPLAT_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_splat.so")
 SPLAT_EXPORTS = ["fn2s_abi_version", "fn2s_forward_warp_forward", "fn2s_forward_warp_forward_det_workspace_bytes",
                  "fn2s_forward_warp_forward_det", "fn2s_forward_warp_backward"]
 FN2S_AUTO, FN2S_GENERAL, FN2S_TILED = 0, 1, 2
 
-# libflownet2_hip_census.so (include/flownet2_hip_census.h): the ternary census distance; the sixth library
+# libflownet2_hip_census.so (include/flownet2_hip_census.h): the ternary census distance
 CENSUS_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_census.so")
 CENSUS_EXPORTS = ["fn2c_abi_version", "fn2c_census_forward", "fn2c_census_backward"]
 
-# libflownet2_hip_smooth.so (include/flownet2_hip_smooth.h): the edge-aware smoothness term; the seventh library
+# libflownet2_hip_smooth.so (include/flownet2_hip_smooth.h): the edge-aware smoothness term
 SMOOTH_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_smooth.so")
 SMOOTH_EXPORTS = ["fn2m_abi_version", "fn2m_smoothness_forward", "fn2m_smoothness_backward"]
 FN2M_EDGE = {"exponential": 0, "gaussian": 1}
 
-_lib = None
-_dbg = None
-_ext = None
-_lookup = None
-_upsample = None
-_splat = None
-_census = None
-_smooth = None
+_INT, _PTR = ctypes.c_int, ctypes.c_void_p
+_RESTYPES = {"fn2_strerror": ctypes.c_char_p, "fn2_debug_set_buffer": None}   # every other entry point returns int or size_t
+# name -> (the global that holds the path (scripts point it at another build before the first call), exports, the names that
+# return size_t, explicit argtypes); "debug" is libflownet2_hip_debug.so, where the size queries keep ctypes' int
+_LIBS = {
+    "": ("LIB_PATH", EXPORTS, ("fn2_multiscale_workspace_bytes", "fn2_correlation_backward_fused_workspace_bytes",
+                               "fn2_resample2d_backward_det_workspace_bytes", "fn2_warp_diff_norm_cat_backward_det_workspace_bytes"),
+         {"fn2_strerror": [_INT]}),
+    "debug": ("DEBUG_LIB_PATH", EXPORTS + DEBUG_EXPORTS, (), {}),
+    "ext": ("EXT_LIB_PATH", EXT_EXPORTS, (), {}),
+    "lookup": ("LOOKUP_LIB_PATH", LOOKUP_EXPORTS, (), {}),
+    "upsample": ("UPSAMPLE_LIB_PATH", UPSAMPLE_EXPORTS, ("fn2u_convex_upsample_backward_workspace_bytes",), {}),
+    "splat": ("SPLAT_LIB_PATH", SPLAT_EXPORTS, ("fn2s_forward_warp_forward_det_workspace_bytes",),
+              {"fn2s_forward_warp_forward_det": [_PTR] * 4 + [ctypes.c_size_t] + [_INT] * 4 + [_PTR]}),
+    "census": ("CENSUS_LIB_PATH", CENSUS_EXPORTS, (),
+               {"fn2c_census_forward": [_PTR] * 3 + [_INT] * 5 + [ctypes.c_float, _INT, _PTR],
+                "fn2c_census_backward": [_PTR] * 5 + [_INT] * 5 + [ctypes.c_float, _INT, _PTR]}),
+    "smooth": ("SMOOTH_LIB_PATH", SMOOTH_EXPORTS, (),
+               {"fn2m_smoothness_forward": [_PTR] * 3 + [_INT] * 7 + [ctypes.c_float, ctypes.c_float, _PTR],
+                "fn2m_smoothness_backward": [_PTR] * 4 + [_INT] * 7 + [ctypes.c_float, ctypes.c_float, _PTR]}),
+}
+_loaded = {}
+
+
+def _load(name):
+    """The library `name` of _LIBS with its return and argument types set, loaded once.  ``import torch`` first so that the HIP
+    runtime torch already mapped (same soname) is the one the kernels register with.  Every library is self-contained: it loads
+    without any of the others."""
+    if name not in _loaded:
+        import torch  # noqa: F401
+        path_global, exports, size_t, argtypes = _LIBS[name]
+        path = globals()[path_global]
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found: run `python flownet2-pytorch_amd/build.py`" +
+                               ("" if name == "debug" else " (the HIP kernels are the only implementation)"))
+        dll = ctypes.CDLL(path)
+        for fn in exports:
+            if name == "debug" and not hasattr(dll, fn):      # (A/B runs load older builds that lack the newer entry points)
+                continue
+            getattr(dll, fn).restype = ctypes.c_size_t if fn in size_t else _RESTYPES.get(fn, _INT)
+        for fn, types in argtypes.items():
+            getattr(dll, fn).argtypes = types
+        _loaded[name] = dll
+    return _loaded[name]
 
 
 def lib():
-    """Loads libflownet2_hip.so.  ``import torch`` first so that the HIP runtime torch already
-    mapped (same soname) is the one the kernels register with."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.fn2_strerror.restype = ctypes.c_char_p
-        _lib.fn2_strerror.argtypes = [ctypes.c_int]
-        for name in EXPORTS[1:]:
-            getattr(_lib, name).restype = ctypes.c_int
-        _lib.fn2_multiscale_workspace_bytes.restype = ctypes.c_size_t
-        _lib.fn2_correlation_backward_fused_workspace_bytes.restype = ctypes.c_size_t
-        _lib.fn2_resample2d_backward_det_workspace_bytes.restype = ctypes.c_size_t
-        _lib.fn2_warp_diff_norm_cat_backward_det_workspace_bytes.restype = ctypes.c_size_t
-    return _lib
+    """libflownet2_hip.so (include/flownet2_hip.h)."""
+    return _load("")
 
 
 def debug_lib():
     """libflownet2_hip_debug.so: the product kernels plus the profiling instantiations (scripts/, ablations)."""
-    global _dbg
-    if _dbg is None:
-        import torch  # noqa: F401
-        if not os.path.exists(DEBUG_LIB_PATH):
-            raise RuntimeError(f"{DEBUG_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py`")
-        _dbg = ctypes.CDLL(DEBUG_LIB_PATH)
-        _dbg.fn2_strerror.restype = ctypes.c_char_p
-        for name in EXPORTS[1:] + DEBUG_EXPORTS:
-            if hasattr(_dbg, name):      # (A/B runs load older builds that lack the newer entry points)
-                getattr(_dbg, name).restype = ctypes.c_int
-        _dbg.fn2_debug_set_buffer.restype = None
-    return _dbg
+    return _load("debug")
 
 
 def ext_lib():
-    """libflownet2_hip_ext.so: Correlation1d (csrc/correlation_1d.hip).  Self-contained; loads without libflownet2_hip.so."""
-    global _ext
-    if _ext is None:
-        import torch  # noqa: F401
-        if not os.path.exists(EXT_LIB_PATH):
-            raise RuntimeError(f"{EXT_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _ext = ctypes.CDLL(EXT_LIB_PATH)
-        for name in EXT_EXPORTS:
-            getattr(_ext, name).restype = ctypes.c_int
-    return _ext
+    """libflownet2_hip_ext.so: Correlation1d (csrc/correlation_1d.hip)."""
+    return _load("ext")
 
 
 def lookup_lib():
-    """libflownet2_hip_lookup.so: CorrLookup (csrc/corr_lookup.hip).  Self-contained; loads without the other two libraries."""
-    global _lookup
-    if _lookup is None:
-        import torch  # noqa: F401
-        if not os.path.exists(LOOKUP_LIB_PATH):
-            raise RuntimeError(f"{LOOKUP_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _lookup = ctypes.CDLL(LOOKUP_LIB_PATH)
-        for name in LOOKUP_EXPORTS:
-            getattr(_lookup, name).restype = ctypes.c_int
-    return _lookup
+    """libflownet2_hip_lookup.so: CorrLookup (csrc/corr_lookup.hip)."""
+    return _load("lookup")
 
 
 def upsample_lib():
-    """libflownet2_hip_upsample.so: ConvexUpsample (csrc/convex_upsample.hip).  Self-contained; loads without the other three libraries."""
-    global _upsample
-    if _upsample is None:
-        import torch  # noqa: F401
-        if not os.path.exists(UPSAMPLE_LIB_PATH):
-            raise RuntimeError(f"{UPSAMPLE_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _upsample = ctypes.CDLL(UPSAMPLE_LIB_PATH)
-        for name in UPSAMPLE_EXPORTS:
-            getattr(_upsample, name).restype = ctypes.c_int
-        _upsample.fn2u_convex_upsample_backward_workspace_bytes.restype = ctypes.c_size_t
-    return _upsample
+    """libflownet2_hip_upsample.so: ConvexUpsample (csrc/convex_upsample.hip)."""
+    return _load("upsample")
 
 
 def splat_lib():
-    """libflownet2_hip_splat.so: ForwardWarp (csrc/forward_warp.hip).  Self-contained; loads without the other four libraries."""
-    global _splat
-    if _splat is None:
-        import torch  # noqa: F401
-        if not os.path.exists(SPLAT_LIB_PATH):
-            raise RuntimeError(f"{SPLAT_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _splat = ctypes.CDLL(SPLAT_LIB_PATH)
-        for name in SPLAT_EXPORTS:
-            getattr(_splat, name).restype = ctypes.c_int
-        _splat.fn2s_forward_warp_forward_det_workspace_bytes.restype = ctypes.c_size_t
-        _splat.fn2s_forward_warp_forward_det.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-    return _splat
+    """libflownet2_hip_splat.so: ForwardWarp (csrc/forward_warp.hip)."""
+    return _load("splat")
 
 
 def census_lib():
-    """libflownet2_hip_census.so: the ternary census distance (csrc/census.hip).  Self-contained; loads without the other five libraries."""
-    global _census
-    if _census is None:
-        import torch  # noqa: F401
-        if not os.path.exists(CENSUS_LIB_PATH):
-            raise RuntimeError(f"{CENSUS_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _census = ctypes.CDLL(CENSUS_LIB_PATH)
-        for name in CENSUS_EXPORTS:
-            getattr(_census, name).restype = ctypes.c_int
-        _census.fn2c_census_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-        _census.fn2c_census_backward.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-    return _census
+    """libflownet2_hip_census.so: the ternary census distance (csrc/census.hip)."""
+    return _load("census")
 
 
 def smooth_lib():
-    """libflownet2_hip_smooth.so: the edge-aware smoothness term (csrc/smooth.hip).  Self-contained; loads without the other six libraries."""
-    global _smooth
-    if _smooth is None:
-        import torch  # noqa: F401
-        if not os.path.exists(SMOOTH_LIB_PATH):
-            raise RuntimeError(f"{SMOOTH_LIB_PATH} not found: run `python flownet2-pytorch_amd/build.py` "
-                               "(the HIP kernels are the only implementation)")
-        _smooth = ctypes.CDLL(SMOOTH_LIB_PATH)
-        for name in SMOOTH_EXPORTS:
-            getattr(_smooth, name).restype = ctypes.c_int
-        _smooth.fn2m_smoothness_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
-        _smooth.fn2m_smoothness_backward.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
-    return _smooth
+    """libflownet2_hip_smooth.so: the edge-aware smoothness term (csrc/smooth.hip)."""
+    return _load("smooth")
 
 
 def check(rc, what):

@@ -1,5 +1,5 @@
-"""CPU-side checks of the census library (include/flownet2_hip_census.h, libflownet2_hip_census.so): what it exports, that it links
-none of the other five libraries, the six headers in one translation unit, every rejection in front of a launch (host pointers,
+"""CPU-side checks of the census library (include/flownet2_hip_census.h, libflownet2_hip_census.so; what it exports and links
+is in tests/test_libraries_host.py): the six headers in one translation unit, every rejection in front of a launch (host pointers,
 no GPU), the refusals at the Python doors, the float64 reference against the PyTorch composition (values and both gradients) and
 in closed form, the arithmetic header (csrc/census_arith.h) as a stand-alone program under the undefined-behaviour sanitizer, and
 the kernels' scratch and LDS budget."""
@@ -19,32 +19,6 @@ import fn2_capi
 
 OK, EINVAL, EDTYPE, EALIGN, EUNSUPPORTED = 0, -1, -2, -3, -4
 U = 2.0 ** -24
-
-
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "flownet2_hip_census.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(fn2c_[a-z0-9_]+)\s*\(", code)))
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted({ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3})
-
-
-def test_census_library_exports_what_its_header_declares():
-    lib = fn2_capi.census_lib()
-    assert lib.fn2c_abi_version() == 1 == RC.header_macros()["FN2C_ABI_VERSION"]
-    exported = _exported(fn2_capi.CENSUS_LIB_PATH)
-    assert exported == _declared(), set(exported) ^ set(_declared())
-    assert sorted(fn2_capi.CENSUS_EXPORTS) == exported
-    assert exported == ["fn2c_abi_version", "fn2c_census_backward", "fn2c_census_forward"]
-    # self-contained: none of the other libraries is a dependency of it
-    dyn = subprocess.run(["readelf", "-d", fn2_capi.CENSUS_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "libflownet2_hip" not in dyn.replace("libflownet2_hip_census.so", "")
-    others = (fn2_capi.EXPORTS + fn2_capi.DEBUG_EXPORTS + fn2_capi.EXT_EXPORTS + fn2_capi.LOOKUP_EXPORTS + fn2_capi.UPSAMPLE_EXPORTS +
-              fn2_capi.SPLAT_EXPORTS)
-    assert not any(n.startswith("fn2c_") for n in others)
 
 
 def test_six_headers_in_one_translation_unit(tmp_path):

@@ -1,5 +1,5 @@
-"""CPU-side checks of Correlation1d's sibling library (include/flownet2_hip_ext.h, libflownet2_hip_ext.so): what it exports, that
-the main library and its ABI are untouched, the shape function, every rejection in front of a launch (host pointers, no GPU),
+"""CPU-side checks of Correlation1d's sibling library (include/flownet2_hip_ext.h, libflownet2_hip_ext.so; what it exports and
+links is in tests/test_libraries_host.py): that the main library and its ABI are untouched, the shape function, every rejection in front of a launch (host pointers, no GPU),
 the float64 reference against the 2-D oracle's centre row, and the tiled kernels' register budget."""
 import ctypes
 import os
@@ -17,25 +17,6 @@ import fn2_capi
 
 OK, EINVAL, EDTYPE, EALIGN, EUNSUPPORTED = 0, -1, -2, -3, -4
 TILED_KERNELS = 30   # forward: 6 wave counts x 3 types; backward: 4 factor brackets x 3 types
-
-
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "flownet2_hip_ext.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(fn2x_[a-z0-9_]+)\s*\(", code)))
-
-
-def test_ext_library_exports_what_its_header_declares():
-    lib = fn2_capi.ext_lib()
-    assert lib.fn2x_abi_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", fn2_capi.EXT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3})
-    assert exported == _declared(), set(exported) ^ set(_declared())
-    assert sorted(fn2_capi.EXT_EXPORTS) == exported
-    assert len(exported) == 4
-    # self-contained: the main library is no dependency of it
-    dyn = subprocess.run(["readelf", "-d", fn2_capi.EXT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "libflownet2_hip.so" not in dyn and "libflownet2_hip_debug.so" not in dyn
 
 
 def test_main_library_untouched():

@@ -1,5 +1,5 @@
-"""CPU-side checks of CorrLookup's library (include/flownet2_hip_lookup.h, libflownet2_hip_lookup.so): what it exports, that it
-links neither of the other two libraries, every rejection in front of a launch (host pointers, no GPU), the float64 reference
+"""CPU-side checks of CorrLookup's library (include/flownet2_hip_lookup.h, libflownet2_hip_lookup.so; what it exports and
+links is in tests/test_libraries_host.py): the three headers in one translation unit, every rejection in front of a launch (host pointers, no GPU), the float64 reference
 against RAFT's all-pairs + grid_sample composition (values and both gradients), and the staged kernels' register budget."""
 import ctypes
 import os
@@ -20,28 +20,6 @@ STAGED_KERNELS = 10   # forward and grad_fmap1, r = 0 .. 4
 
 # (H, W, H2, W2, r, C)
 GEOMETRIES = [(5, 6, 5, 6, 2, 3), (4, 7, 2, 3, 1, 5), (3, 4, 3, 4, 0, 2), (4, 5, 2, 2, 4, 4)]
-
-
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "flownet2_hip_lookup.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(fn2l_[a-z0-9_]+)\s*\(", code)))
-
-
-def test_lookup_library_exports_what_its_header_declares():
-    lib = fn2_capi.lookup_lib()
-    assert lib.fn2l_abi_version() == 1 == RL.header_macros()["FN2L_ABI_VERSION"]
-    out = subprocess.run(["nm", "-D", "--defined-only", fn2_capi.LOOKUP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3})
-    assert exported == _declared(), set(exported) ^ set(_declared())
-    assert sorted(fn2_capi.LOOKUP_EXPORTS) == exported
-    assert len(exported) == 3
-    # self-contained: neither other library is a dependency of it
-    dyn = subprocess.run(["readelf", "-d", fn2_capi.LOOKUP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "libflownet2_hip" not in dyn.replace("libflownet2_hip_lookup.so", "")
-    # and the other two did not grow
-    assert len(fn2_capi.EXPORTS) == 31 and len(fn2_capi.EXT_EXPORTS) == 4
-    assert not any(n.startswith("fn2l_") for n in fn2_capi.EXPORTS + fn2_capi.DEBUG_EXPORTS + fn2_capi.EXT_EXPORTS)
 
 
 def test_three_headers_in_one_translation_unit(tmp_path):

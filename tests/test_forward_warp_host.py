@@ -1,5 +1,5 @@
-"""CPU-side checks of ForwardWarp's library (include/flownet2_hip_splat.h, libflownet2_hip_splat.so): what it exports, that it
-links none of the other four libraries, the five headers in one translation unit, every rejection in front of a launch (host
+"""CPU-side checks of ForwardWarp's library (include/flownet2_hip_splat.h, libflownet2_hip_splat.so; what it exports and
+links is in tests/test_libraries_host.py): its workspace size, the five headers in one translation unit, every rejection in front of a launch (host
 pointers, no GPU), the refusals at the Python doors, the float64 reference against the PyTorch composition (values and both
 gradients) and in closed form, the tap computation (csrc/splat_taps.h) as a stand-alone program under the undefined-behaviour
 sanitizer, and the kernels' scratch and LDS budget."""
@@ -18,37 +18,6 @@ import forward_warp_ref as RS
 import fn2_capi
 
 OK, EINVAL, EDTYPE, EALIGN, EUNSUPPORTED = 0, -1, -2, -3, -4
-
-
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "flownet2_hip_splat.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(fn2s_[a-z0-9_]+)\s*\(", code)))
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted({ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3})
-
-
-def test_splat_library_exports_what_its_header_declares():
-    lib = fn2_capi.splat_lib()
-    assert lib.fn2s_abi_version() == 1 == RS.header_macros()["FN2S_ABI_VERSION"]
-    exported = _exported(fn2_capi.SPLAT_LIB_PATH)
-    assert exported == _declared(), set(exported) ^ set(_declared())
-    assert sorted(fn2_capi.SPLAT_EXPORTS) == exported
-    assert exported == ["fn2s_abi_version", "fn2s_forward_warp_backward", "fn2s_forward_warp_forward", "fn2s_forward_warp_forward_det",
-                        "fn2s_forward_warp_forward_det_workspace_bytes"]
-    # self-contained: none of the other libraries is a dependency of it
-    dyn = subprocess.run(["readelf", "-d", fn2_capi.SPLAT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "libflownet2_hip" not in dyn.replace("libflownet2_hip_splat.so", "")
-    # and the other four did not grow
-    fn2_capi.lib(), fn2_capi.ext_lib(), fn2_capi.lookup_lib(), fn2_capi.upsample_lib()
-    for path, names, n in ((fn2_capi.LIB_PATH, fn2_capi.EXPORTS, 31), (fn2_capi.EXT_LIB_PATH, fn2_capi.EXT_EXPORTS, 4),
-                           (fn2_capi.LOOKUP_LIB_PATH, fn2_capi.LOOKUP_EXPORTS, 3), (fn2_capi.UPSAMPLE_LIB_PATH, fn2_capi.UPSAMPLE_EXPORTS, 4)):
-        assert _exported(path) == sorted(names) and len(names) == n, path
-    others = fn2_capi.EXPORTS + fn2_capi.DEBUG_EXPORTS + fn2_capi.EXT_EXPORTS + fn2_capi.LOOKUP_EXPORTS + fn2_capi.UPSAMPLE_EXPORTS
-    assert not any(n.startswith("fn2s_") for n in others)
 
 
 def test_workspace_bytes():
