@@ -185,3 +185,28 @@ def test_resample_backward_halo_plane_model():
     assert m["pass1_us"] >= halo.NO_FLUSH_US                             # the scatter floor is in both designs
     # brute force of the plane traffic on a small field: non-zero segments = distinct (tile, row, segment) triples, as in the atomic model
     assert counts["flush_req"] * 8 * 64 == int(round(m["plane_MB"] * 1e6))
+
+
+# ---- fp32 matrix backward: 64- or 32-channel groups (csrc/correlation_mfma_bwd.hip corr_backward_mfma_f32)
+def test_fp32_backward_channel_group_choice():
+    """tests/corr_general_ref.py bwd_groups64 restates the occupancy test of corr_backward_mfma_f32.  (8, 64, 64, 8): B * NRG * NXT =
+    64, base 256, both group sizes fill whole rounds of 256 workgroups, so FN2_CORR_MFMA_F32 keeps 64-channel groups
+    (mb::launch_nv<4>); (2, 64, 12, 16) and every C % 64 == 0 shape of test_gpu_parity.py's BWD_CASES fill less than one round,
+    where twice the workgroups are twice the occupancy, and drop to 32-channel groups.  The forcing tunes (debug algos 101 / 102)
+    ignore the occupancy."""
+    import ast
+    import corr_general_ref as G
+    s = src("correlation_mfma_bwd.hip")
+    assert "const long r = (t + 255) / 256; return r ? (double)t / (double)(r * 256) : 1.0;" in s
+    assert "round_eff(base * (C / 32)) > 1.1 * round_eff(base * (C / 64))" in s
+    assert "const long base = (long)B * 2 * a.NRG * a.NXT * (fused ? 2 : 1);" in s and "a.NRG = (H / 2 + 3) / 4;" in s
+    assert "bool g64 = (C % 64 == 0) && tune != 1;" in s and "constexpr int TILE_X = 64;" in s
+    assert G.bwd_groups64(8, 64, 64, 8) and G.bwd_groups64(8, 64, 64, 8, tune=2) and not G.bwd_groups64(8, 64, 64, 8, tune=1)
+    assert not G.bwd_groups64(2, 64, 12, 16) and G.bwd_groups64(2, 64, 12, 16, tune=2)
+    assert not G.bwd_groups64(1, 128, 10, 18) and G.bwd_groups64(1, 128, 10, 18, tune=2)
+    with open(os.path.join(HERE, "test_gpu_parity.py")) as f:
+        cases = ast.literal_eval(re.search(r"^BWD_CASES = (\[.*?^\])", f.read(), re.S | re.M).group(1))
+    assert len(cases) >= 11 and sum(c[1] % 64 == 0 for c in cases) >= 4
+    for B, C, H, W, md in cases:
+        assert not G.bwd_groups64(B, C, H, W), (B, C, H, W)
+        assert G.bwd_groups64(B, C, H, W, tune=2) == (C % 64 == 0)
