@@ -66,23 +66,40 @@ int fn2m_abi_version(void); /* FN2M_ABI_VERSION */
  *
  * Per-element bounds against the float64 evaluation on the fp32 inputs, u = 2^-24.  Per valid cell and flow channel S = 0 for
  * order 1 and S = |f[x + 2] - f[x + 1]| + |f[x + 1] - f[x]| for order 2 (the second difference cancels: its error scales with S):
- *   forward    |err out| <= sum_f [ u ((FN2M_BOUND_A + FN2M_BOUND_E e) w rho + 2 w S) + 2^-126 rho ]
+ *   forward    |err out| <= sum_f [ u ((FN2M_BOUND_A + FN2M_BOUND_E e) w rho + 2 w S) + 2^-126 rho ] + 2^-149 [0 < out < 2^-125]
  *   gradient   |err grad_flow[q]| <= u sum over the taps reaching q of |coef| T,
- *              T = |gO'| (w ((FN2M_BOUND_A + FN2M_BOUND_E e) |rho'| + 2 S eps^2 / rho^3) + 2^-126 / u),   eps^2 / rho^3 = 0 for eps = 0
- * with FN2M_BOUND_A = 24 and FN2M_BOUND_E = 16; where the bound is 0 the value is exactly 0.  Derivation from the list above:
+ *              T = |gO'| (w ((FN2M_BOUND_A + FN2M_BOUND_E e) |rho'| + max(2 S eps^2 / rho^3, 2 D / u)) + 2^-126 / u)
+ *                  + 2^-149 / u [0 < |t| < 2^-125]
+ *              dd = u |d| (order 1) or u ((1 + u) S + |d|) (order 2), the most the computed d can be off;
+ *              eps > 0: D = min(2, dd eps^2 / (max(|d| - dd, 0)^2 + eps^2)^(3/2)), and eps^2 / rho^3 is rho''(d);
+ *              eps = 0: D = 2 where |d| <= dd and dd > 0, else 0, and eps^2 / rho^3 = 0
+ * with FN2M_BOUND_A = 24 and FN2M_BOUND_E = 16; [c] is 1 where c holds and 0 elsewhere, out and t the exact values; where the
+ * bound is 0 the value is exactly 0.  Derivation from the list above:
  *   e        every a_c >= 0, so relative errors add: dI 1 u, t 1 u (gaussian: t t doubles them and adds one: 5 u), the two sums
  *            2 u, the mean 1.5 u (fl32(1/3) is 0.5 u off), the scaling by fl32(log2 e) 1.25 u: below 7 u (exponential) and
  *            10 u (gaussian) of e.  An error delta in exp2's argument is a relative error delta ln 2 in w: below 10 e u.
- *   w        that, and exp2 within 1 ulp (2 u): (2 + 10 e) u.
- *   d        order 1: 1 u |d|.  Order 2: u |f[x+2] - f[x+1]| + u |f[x+1] - f[x]| + u |d| = u (S + |d|).
+ *   w        that, and exp2 within 1 ulp (2 u): (2 + 10 e) u.  Below 2^-126 the computed w is 0 and the exact one is less than
+ *            2^-126: the 2^-126 terms.
+ *   d        order 1: 1 u |d|.  Order 2: the two inner differences are u |f[x+2] - f[x+1]| and u |f[x+1] - f[x]| off, the outer
+ *            one rounds what it gets, at most (1 + u) S + |d|: dd.
  *   rho      |rho'| <= 1 and |d| <= rho turn d's error into u (rho + S); d d, eps2 (1.5 u) and the sum are 3.5 u of rho^2, halved
  *            by the root, which adds 2 u: 4.75 u rho + u S.  The sum over f up to 3 u, the product with w 1 u:
- *            forward <= u ((10.75 + 10 e) w rho + w S) per channel, inside 24 + 16 e and 2 S.
- *   rho'     rho'' = eps^2 / rho^3 turns d's error into u (|d| + S) eps^2 / rho^3 <= u (|rho'| + S eps^2 / rho^3); the sum under
- *            rsq 1.75 u, rsq 2 u, the product 1 u: 5.75 u |rho'| + u S eps^2 / rho^3.
- *   t        gO' w 1 u, times rho' 1 u: u |gO'| w ((9.75 + 10 e) |rho'| + S eps^2 / rho^3); the gather's five additions at most
- *            5 u of sum |coef| |t|: inside T.
- * These are worst cases; the test inputs stay below half of them, typically far below.
+ *            forward <= u ((10.75 + 10 e) w rho + w S) per channel, inside 24 + 16 e and 2 S.  A product below 2^-126 is
+ *            rounded to a multiple of 2^-149 instead: the last term.
+ *   rho'     rho' moves by at most D when d moves by dd.  eps > 0: rho'' = eps^2 / (d^2 + eps^2)^(3/2) decreases in |d|, so over
+ *            [|d| - dd, |d| + dd] it is at most its value at max(|d| - dd, 0), and rho' as a whole lies in [-1, 1]: D.  eps = 0:
+ *            the computed d has the sign of d wherever |d| > dd; elsewhere rho' is one of {-1, 0, +1}, at most 2 off.  (Up to
+ *            ABI 1's first revision this line read "rho'' turns d's error into u (|d| + S) eps^2 / rho^3", the first-order
+ *            term at d itself, and 0 for eps = 0.  That holds only while dd is small against max(|d|, eps): on a flow
+ *            2^20 x + 0.05 N(0, 1), where u S = 1/8, a correct fp32 evaluation leaves it by 10^5 at eps = 0 and by 10^3 at
+ *            eps = 0.001.  The old term stays inside the max, so this bound is nowhere below the old one; on flows of
+ *            magnitude 20 the two differ by at most 1.06.)  The sum under rsq 1.75 u, rsq 2 u, the product 1 u, of the computed
+ *            |rho'| <= |rho'| + D: 4.75 u |rho'| + (1 + 4.75 u) D.
+ *   t        gO' w 1 u, times rho' 1 u: u |gO'| w ((8.75 + 10 e) |rho'| + (1 + 11 u + 10 e u) D / u), inside T as long as
+ *            e < 2^20 (beyond that w rounds to 0 in float64 as well); either product, once below 2^-126, is rounded to a
+ *            multiple of 2^-149: together the last term.  The gather's five additions at most 5 u of sum |coef| |t|: inside T.
+ * These are worst cases; flows and images of ordinary magnitude stay below half of them, typically far below, and the flows that
+ * cancel, the graded magnitudes and the flushed weights stay inside them.
  *
  * Kernels: a workgroup of 256 lanes owns FN2M_TILE_H x FN2M_TILE_W output pixels, a wave four rows of it, a lane four vertically
  * adjacent pixels of one column.  The flow and image planes of the tile are staged in LDS, the forward with k rows below and

@@ -69,6 +69,10 @@ int fn2s_abi_version(void); /* FN2S_ABI_VERSION */
  *               |err| <= (C + FN2S_K_F) 2^-23 sum_c |input_c| (by (|gO01| + |gO00|) + ay (|gO11| + |gO10|)) + (C + FN2S_K_F) 2^-149
  *               and likewise for y with bx, ax and the pairs (10, 00), (11, 01)
  * The 2^-149 terms stand for roundings into the subnormal range, for operands up to 1 in magnitude.
+ * Results below 2^-126: the fp32 atomic adds of both kernels and the LDS adds of the tiled one keep subnormal sums on gfx950
+ * (measured: planes whose every value, and so every sum, is subnormal stay inside the bound above under FN2S_GENERAL, FN2S_TILED
+ * and FN2S_AUTO, where a sum flushed to 0 would miss its (n + 2) 2^-149 by a factor of 10^6), so the floor holds
+ * as written over the whole domain.  The deterministic forward keeps its bits there too: plane maxima from 2^-127 to 2^126.
  *
  * Kernels (`algo` of fn2s_forward_warp_forward):
  *   FN2S_GENERAL  one lane per source pixel, lanes along x, a loop over channels, one float atomic add per tap inside the

@@ -1,6 +1,7 @@
 """float64 reference of the ternary census distance (include/flownet2_hip_census.h), written from the header's formulas with numpy
 shifts -- not from the kernels' tiling; ``compose``, the PyTorch composition (identity-filter ``conv2d`` unfold, soft sign, robust
-distance, mean or sum, border mask); and the input family the tests share.  Test infrastructure only.
+distance, mean or sum, border mask); ``emulate``, the header's operation list in numpy float32; and the image families the tests
+share.  Test infrastructure only.
 
 The grey intensities are restated in numpy float32 in the header's operation order, so that everything after them starts from the
 numbers the kernels start from; everything after them is float64.
@@ -187,3 +188,135 @@ def image_pair(shape, seed):
     im2 = np.clip(im1 + 0.05 * rng.standard_normal(shape), 0.0, 1.0).astype(np.float32)
     go = rng.standard_normal((N, 1, H, W)).astype(np.float32)
     return im1, im2, go
+
+
+FAMILIES = ("noise", "knee", "opposed", "flat", "graded", "seams")
+GRADED_EXPONENTS = (-130, -40, -12, 0, 12, 40, 59)
+GRADED_BAND = 10
+# (family, scale) as the tests run them: every family at its own scale, ``noise`` and ``seams`` at further ones
+FAMILY_SCALES = (("noise", 255.0), ("noise", -255.0), ("noise", 1.0), ("noise", 2.0 ** -30), ("knee", 255.0), ("opposed", 255.0),
+                 ("flat", 255.0), ("graded", 1.0), ("seams", 255.0), ("seams", 1.0))
+
+
+def grad_out(shape, seed):
+    """N x 1 x H x W float32, standard normal."""
+    return np.random.default_rng(seed).standard_normal((shape[0], 1) + tuple(shape[2:])).astype(np.float32)
+
+
+def _taps(g, md):
+    """K - 1 x N x h x w float64: x = g[p + k] - g[p] of every interior pixel p and offset k."""
+    g = np.asarray(g, np.float64)
+    H, W = g.shape[-2:]
+    return np.stack([g[:, md + dy:H - md + dy, md + dx:W - md + dx] - g[:, md:H - md, md:W - md] for dy, dx in offsets(md)])
+
+
+def image_family(name, shape, seed):
+    """(im1, im2, scale): float32 N x C x H x W each, and the scale the family is meant for.  Each family asserts on its own
+    output what it is for (on planes of at least 17 x 67, max_distance 3), so that a change of constants cannot turn it benign:
+      noise    ``image_pair``: im1 uniform in [0, 1), im2 = im1 + 5 % noise; scale 255
+      knee     a contrast of 2 / 255 around 0.5, im2 = im1 + noise of a quarter of that: the grey differences stay where f' > 0.1
+      opposed  im2 = 1 - im1: f_1 and f_2 have opposite signs, |d| near 2
+      flat     im1 constant 0.25, im2 = im1 + 2^-21 N(0, 1): an output below 10^-5
+      graded   scale 1; column bands of GRADED_BAND columns carry magnitudes 2^e, e cycling through GRADED_EXPONENTS, im1 uniform in
+               [1/4, 1) times that, im2 = im1 (1 + 5 % noise): subnormal intensities next to intensities of 2^59
+      seams    a +-1 checkerboard of period 1 left of column 64 and, right of it, a single step between rows 15 and 16; im2 is im1
+               moved by one column: transitions on the tile seams.  Meant for scale 255 and scale 1."""
+    N, C, H, W = shape
+    rng = np.random.default_rng(seed)
+    big = H >= 17 and W >= 67
+    scale = 255.0
+    if name == "noise":
+        im1, im2, _ = image_pair(shape, seed)
+    elif name == "knee":
+        im1 = (0.5 + (2.0 / 255) * (rng.random(shape) - 0.5)).astype(np.float32)
+        im2 = (im1 + (0.5 / 255) * rng.standard_normal(shape)).astype(np.float32)
+        if big:
+            x1 = _taps(grey(im1, scale), 3)
+            assert (np.abs(x1) < 1.75).mean() >= 0.5 and df(1.75) > 0.1
+    elif name == "opposed":
+        im1 = rng.random(shape).astype(np.float32)
+        im2 = (np.float32(1) - im1).astype(np.float32)
+        if big:
+            d = f(_taps(grey(im1, scale), 3)) - f(_taps(grey(im2, scale), 3))
+            assert np.median(np.abs(d)) > 1.5
+    elif name == "flat":
+        im1 = np.full(shape, 0.25, np.float32)
+        im2 = (im1 + 2.0 ** -21 * rng.standard_normal(shape)).astype(np.float32)
+        if big:
+            out = forward(im1, im2, 3, scale, True)
+            assert out.max() > 0 and out.max() < 1e-5
+    elif name == "graded":
+        scale = 1.0
+        band = np.array(GRADED_EXPONENTS, np.float64)[(np.arange(W) // GRADED_BAND) % len(GRADED_EXPONENTS)]
+        im1 = ((0.25 + 0.75 * rng.random(shape)) * 2.0 ** band).astype(np.float32)
+        im2 = (im1.astype(np.float64) * (1 + 0.05 * rng.standard_normal(shape))).astype(np.float32)
+        if big:
+            for im in (im1, im2):
+                g = np.abs(grey(im, scale).astype(np.float64))
+                assert 2.0 ** 57 <= g.max() < 2.0 ** 60, g.max()
+            tiny = (np.abs(im1) < 2.0 ** -126) & (im1 != 0)
+            assert tiny.mean() >= 0.05
+    elif name == "seams":
+        yy, xx = np.mgrid[0:H, 0:W]
+        plane = np.where(xx < 64, 1.0 - 2.0 * ((xx + yy) % 2), np.where(yy < 16, 1.0, -1.0)).astype(np.float32)
+        im1 = np.broadcast_to(plane, shape).copy()
+        im2 = np.roll(im1, 1, axis=3)
+        if big:
+            assert (im1[..., 15, 64:] != im1[..., 16, 64:]).all() and (im1[..., 15, :64] != im1[..., 16, :64]).all()
+            assert (im1[..., :, 63] != im1[..., :, 64]).any() and (im1[..., :, 62] != im1[..., :, 63]).all()
+    else:
+        raise ValueError(f"no image family {name!r}")
+    assert im1.dtype == im2.dtype == np.float32 and np.isfinite(im1).all() and np.isfinite(im2).all()
+    return im1, im2, scale
+
+
+# ------------------------------------------------------------------ the header's operation list in float32
+def emulate(im1, im2, go, md=3, scale=255.0, normalize=True, mutate=None):
+    """(out, grad_im1, grad_im2) in float32, following include/flownet2_hip_census.h operation by operation in numpy float32
+    (every operation rounded on its own, rsq and rcp correctly rounded), in the header's summation order.  ``mutate`` plants
+    one mistake, for the tests that show which family catches it:
+      "clamped_grey"  the grey intensity clamped to [0, 255], as if every image were in [0, 1] and every scale 255
+      "abs_scale"     the gradient scaled by |scale| instead of scale"""
+    f32 = np.float32
+    im1, im2 = np.asarray(im1, f32), np.asarray(im2, f32)
+    N, C, H, W = im1.shape
+    s = f32(scale)
+
+    def grey_of(im):
+        return np.clip(grey(im, scale), f32(0), f32(255)) if mutate == "clamped_grey" else grey(im, scale)
+
+    def rsq(v):
+        return (1.0 / np.sqrt(v.astype(np.float64))).astype(f32)
+
+    def rcp(v):
+        return (1.0 / v.astype(np.float64)).astype(f32)
+
+    g1, g2 = grey_of(im1), grey_of(im2)
+    w = f32(1.0 / (2 * md + 1) ** 2) if normalize else f32(1)
+    ins = inner(H, W, md)
+    gop = np.where(ins, np.asarray(go, f32)[:, 0], f32(0))
+    total, a1, a2 = np.zeros((N, H, W), f32), np.zeros((N, H, W), f32), np.zeros((N, H, W), f32)
+    with np.errstate(under="ignore"):
+        for dx in range(-md, md + 1):
+            col, c1, c2 = np.zeros((N, H, W), f32), np.zeros((N, H, W), f32), np.zeros((N, H, W), f32)
+            for dy in range(-md, md + 1):
+                if (dy, dx) == (0, 0):
+                    continue
+                # forward: x = g[p + k] - g[p]
+                x1, x2 = _shift(g1, dy, dx) - g1, _shift(g2, dy, dx) - g2
+                d = x1 * rsq(f32(0.81) + x1 * x1) - x2 * rsq(f32(0.81) + x2 * x2)
+                d2 = d * d
+                col = col + d2 * rcp(f32(0.1) + d2)
+                # backward: x = g[q] - g[q + k]
+                x1, x2 = g1 - _shift(g1, dy, dx), g2 - _shift(g2, dy, dx)
+                r1, r2 = rsq(f32(0.81) + x1 * x1), rsq(f32(0.81) + x2 * x2)
+                d = x1 * r1 - x2 * r2
+                q = rcp(f32(0.1) + d * d)
+                t = (gop + _shift(gop, dy, dx)) * ((f32(0.2) * d) * (q * q))
+                c1 = c1 + t * (f32(0.81) * ((r1 * r1) * r1))
+                c2 = c2 - t * (f32(0.81) * ((r2 * r2) * r2))
+            total, a1, a2 = total + col, a1 + c1, a2 + c2
+        out = np.where(ins, w * total, f32(0))[:, None]
+        sg = np.abs(s) if mutate == "abs_scale" else s
+        cw = np.array(CW if C == 3 else [f32(1)], f32)[None, :, None, None] * sg if C == 3 else np.full((1, 1, 1, 1), sg, f32)
+        return out.astype(f32), (cw * (w * a1)[:, None]).astype(f32), (cw * (w * a2)[:, None]).astype(f32)

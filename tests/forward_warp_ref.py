@@ -1,6 +1,6 @@
 """float64 reference of ForwardWarp (include/flownet2_hip_splat.h), written from the header's formulas with numpy scatter-adds --
-not from the kernels' tiling; ``compose``, the PyTorch composition (``index_put_(accumulate=True)`` over the four taps); and the
-flow families the tests share.  Test infrastructure only.
+not from the kernels' tiling; ``compose``, the PyTorch composition (``index_put_(accumulate=True)`` over the four taps); the
+header's sums emulated in numpy float32; and the flow and input families the tests share.  Test infrastructure only.
 
 The fp32 values of fx, fy, ax, ay, bx, by are taken as the header defines them; everything after them is float64, except the
 fixed-point result of the deterministic contract, which restates the fp32 contributions and sums them exactly in int64.
@@ -76,9 +76,10 @@ def forward_bound(S, n):
     return (n + 2) * U23 * S + (n + 2) * SUB
 
 
-def forward_fixed(inp, flow):
+def forward_fixed(inp, flow, mutate=None):
     """The deterministic contract's result, float32 B x C x H x W, computed exactly: the fp32 contributions v = fl32(fl32(w) x),
-    q = rne(v 2^s) as int64 with s = 62 - E - K per plane, exact integer sums, (float)((double)Q 2^-s)."""
+    q = rne(v 2^s) as int64 with s = 62 - E - K per plane, exact integer sums, (float)((double)Q 2^-s).  ``mutate="float_scale"``
+    plants a mistake for the tests' teeth: v 2^s formed in float32 with 2^s as a float32 of its own."""
     inp = np.asarray(inp, dtype=np.float32)
     B, C, H, W = inp.shape
     t = taps(flow)
@@ -100,7 +101,12 @@ def forward_fixed(inp, flow):
                 m, yy, xx = _inside(t, dy, dx, H, W)
                 y, x = np.nonzero(m[b] & (w[b] != 0))
                 v = (w[b, y, x] * inp[b, c, y, x]).astype(np.float32)
-                q = np.rint(np.ldexp(v.astype(np.float64), s)).astype(np.int64)
+                if mutate == "float_scale":
+                    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+                        scaled = (v * np.float32(2.0 ** s if s < 128 else np.inf)).astype(np.float32).astype(np.float64)
+                    q = np.rint(np.where(np.isfinite(scaled), scaled, 0.0)).astype(np.int64)
+                else:
+                    q = np.rint(np.ldexp(v.astype(np.float64), s)).astype(np.int64)
                 np.add.at(Q, (yy[b, y, x], xx[b, y, x]), q)
             out[b, c] = np.ldexp(Q.astype(np.float64), -s).astype(np.float32)
     return out
@@ -185,3 +191,134 @@ def inside_share(flow):
     B, _, H, W = flow.shape
     t = taps(flow)
     return sum(_inside(t, dy, dx, H, W)[0].sum() for dy, dx in TAPS) / (4.0 * B * H * W)
+
+
+# ---- the input families of the tests (seeded, float32)
+INPUT_FAMILIES = ("normal", "graded", "cancel", "subnormal", "huge")
+GRADED_EXPONENTS = (-100, -20, 0, 20, 100)
+# the flows each input family is combined with: a plane maximum of 2^126 cannot take the converge flow's H W terms in one cell
+FAMILY_FLOWS = {"normal": ("smooth", "converge", "shift"), "graded": ("smooth", "converge", "shift"), "cancel": ("smooth", "converge", "shift"),
+                "subnormal": ("smooth", "converge", "shift"), "huge": ("smooth", "zero", "shift")}
+
+
+def input_family(name, shape, seed):
+    """(input, grad_out), float32 B x C x H x W each.  Each family asserts on its own output -- with the flows of ``flow_family``
+    it is meant for -- that it still does what it is for:
+      normal     standard normal, both
+      graded     plane (b, c) scaled by 2^e, e cycling through GRADED_EXPONENTS with b C + c; grad_out standard normal / 8 scaled
+                 by 2^-e: every product of the gradients stays below 2^100
+      cancel     signs alternate from source pixel to source pixel, magnitudes in [1, 1 + 2^-10]: under ``converge`` the cells
+                 that receive everything hold |sum| <= 2^-6 sum |w v|
+      subnormal  planes alternate between |v| in (0, 2^-127] and |v| in [2^-125, 2^-120]: every value of the first kind is
+                 subnormal, and under ``smooth`` at least 10 % of the second kind's contributions are
+      huge       every plane's maximum in [2^125, 2^126): under ``smooth``, ``zero`` and ``shift`` every cell's sum |w v| stays
+                 below 2^127, so no partial sum in any order overflows"""
+    B, C, H, W = shape
+    rng = np.random.default_rng(seed)
+    inp = rng.standard_normal(shape)
+    go = rng.standard_normal(shape)
+    plane = (np.arange(B)[:, None] * C + np.arange(C)[None, :])[:, :, None, None]
+    if name == "normal":
+        pass
+    elif name == "graded":
+        e = np.array(GRADED_EXPONENTS, np.float64)[plane % len(GRADED_EXPONENTS)]
+        inp, go = inp * 2.0 ** e, go / 8 * 2.0 ** -e
+        assert np.abs(inp).max() < 2.0 ** 103 and np.abs(go).max() < 2.0 ** 100 and np.abs(inp * go).max() < 2.0 ** 100
+        assert (np.abs(inp).max(axis=(2, 3)) * np.abs(go).max(axis=(2, 3))).max() * C < 2.0 ** 100
+    elif name == "cancel":
+        sign = 1.0 - 2.0 * (np.arange(H * W).reshape(H, W) % 2)
+        inp = sign * (1 + 2.0 ** -10 * rng.random(shape))
+    elif name == "subnormal":
+        tiny = 2.0 ** -127 * (2.0 ** -22 + (1 - 2.0 ** -22) * rng.random(shape)) * np.sign(inp)
+        small = 2.0 ** (-125 + 5 * rng.random(shape)) * np.sign(inp)
+        inp = np.where(plane % 2 == 0, tiny, small)
+    elif name == "huge":
+        inp = inp / np.abs(inp).max(axis=(2, 3), keepdims=True) * 2.0 ** 125 * (1 + rng.random((B, C, 1, 1)) * (1 - 2.0 ** -20))
+    else:
+        raise ValueError(name)
+    inp, go = inp.astype(np.float32), go.astype(np.float32)
+    assert np.isfinite(inp).all() and np.isfinite(go).all()
+    if H * W >= 17 * 67:
+        if name == "cancel":
+            out, S, n = forward(inp, flow_family("converge", B, H, W))
+            full = n == H * W
+            assert full.any() and (np.abs(out[full]) <= 2.0 ** -6 * S[full]).all()
+        if name == "subnormal":
+            a = np.abs(inp.astype(np.float64))
+            first = np.broadcast_to(plane % 2 == 0, shape)
+            assert (a[first] > 0).all() and (a[first] <= 2.0 ** -127).all() and (a[~first] >= 2.0 ** -125).all() and (a[~first] <= 2.0 ** -120).all()
+            t = taps(flow_family("smooth", B, H, W))
+            below = total = 0
+            for (dy, dx), w in zip(TAPS, _weights(t, np.float64)):
+                m = _inside(t, dy, dx, H, W)[0] & (w != 0)
+                v = np.abs(w[:, None] * a)[np.broadcast_to(m[:, None], shape) & ~first]
+                below, total = below + (v < 2.0 ** -126).sum(), total + v.size
+            assert below >= 0.1 * total, (below, total)
+        if name == "huge":
+            top = np.abs(inp.astype(np.float64)).max(axis=(2, 3))
+            assert (top >= 2.0 ** 125).all() and (top < 2.0 ** 126).all()
+            for fl in FAMILY_FLOWS["huge"]:
+                assert forward(inp, flow_family(fl, B, H, W))[1].max() < 2.0 ** 127
+    return inp, go
+
+
+# ---- the header's operation list in float32
+def emulate_forward(inp, flow, mutate=None):
+    """The atomic forward in numpy float32: every contribution fl32(fl32(w) x) added to its cell in float32, one rounding per
+    addition, in the order of the source pixels, tap by tap -- one of the orders the atomics may take.  ``mutate="ftz_add"``
+    plants a mistake: an addition whose result is subnormal gives 0."""
+    inp = np.asarray(inp, np.float32)
+    B, C, H, W = inp.shape
+    t = taps(flow)
+    out = np.zeros((B, C, H, W), np.float32)
+    tiny = np.float32(2.0 ** -126)
+    with np.errstate(under="ignore"):
+        for (dy, dx), w in zip(TAPS, _weights(t, np.float32)):
+            m, yy, xx = _inside(t, dy, dx, H, W)
+            b, y, x = np.nonzero(m & (w != 0))
+            for c in range(C):
+                v = (w[b, y, x] * inp[b, c, y, x]).astype(np.float32)
+                if mutate == "ftz_add":
+                    for i in range(v.size):
+                        s = np.float32(out[b[i], c, yy[b[i], y[i], x[i]], xx[b[i], y[i], x[i]]] + v[i])
+                        out[b[i], c, yy[b[i], y[i], x[i]], xx[b[i], y[i], x[i]]] = s if abs(s) >= tiny else np.float32(0)
+                else:
+                    np.add.at(out[:, c], (b, yy[b, y, x], xx[b, y, x]), v)
+    return out
+
+
+def emulate_backward(inp, flow, go):
+    """(grad_input, grad_flow) in numpy float32, the header's sums operation by operation: every sum from +0, one rounding per
+    operation, taps in the order 00, 01, 10, 11, channels ascending."""
+    f32 = np.float32
+    inp, go = np.asarray(inp, f32), np.asarray(go, f32)
+    B, C, H, W = inp.shape
+    t = taps(flow)
+    g = []
+    bidx, cidx = np.arange(B)[:, None, None, None], np.arange(C)[None, :, None, None]
+    for dy, dx in TAPS:
+        m, yy, xx = _inside(t, dy, dx, H, W)
+        yy, xx = np.where(m, yy, 0), np.where(m, xx, 0)
+        g.append(np.where(m[:, None], go[bidx, cidx, yy[:, None], xx[:, None]], f32(0)))
+    with np.errstate(under="ignore"):
+        w = [x[:, None] for x in _weights(t, f32)]
+        gi = np.zeros((B, C, H, W), f32)
+        for k in range(4):
+            gi = gi + w[k] * g[k]
+        ax, ay, bx, by = (t[k][:, None] for k in ("ax", "ay", "bx", "by"))
+        g00, g01, g10, g11 = g
+        tx = inp * (by * (g01 - g00) + ay * (g11 - g10))
+        ty = inp * (bx * (g10 - g00) + ax * (g11 - g01))
+        gfx, gfy = np.zeros((B, H, W), f32), np.zeros((B, H, W), f32)
+        for c in range(C):
+            gfx, gfy = gfx + tx[:, c], gfy + ty[:, c]
+    return gi, np.stack([gfx, gfy], 1)
+
+
+def fixed_bound(inp, S, n):
+    """What the header promises of the deterministic forward: the forward bound plus 2^(K - 62) M per contribution."""
+    inp = np.asarray(inp, np.float32)
+    H, W = inp.shape[2:]
+    K = (H * W - 1).bit_length()
+    M = np.abs(inp.astype(np.float64)).max(axis=(2, 3), keepdims=True)
+    return forward_bound(S, n) + n * 2.0 ** (K - 62) * M

@@ -326,3 +326,74 @@ def test_kernels_use_no_scratch_and_their_lds_is_the_headers_formula(tmp_path):
         seen.add((kind, md))
     assert seen == {(k, d) for k in ("fwd", "bwd") for d in (1, 2, 3)}
     assert RC.lds_bytes(2, 3) == 12496 and RC.lds_bytes(3, 3) == 18744 <= 64 * 1024
+
+
+# ------------------------------------------------------------------ the image families
+_FAMILY_SHAPES = ((1, 1, 17, 67), (2, 3, 33, 130))
+_FAMILY_CONFIGS = ((1, True), (3, False), (3, True))
+
+
+def _emulated_ratios(shape, family, scale, md, normalize, mutate=None):
+    """Largest error / bound of the float32 emulation of the header's operation list: (forward, grad_im1, grad_im2); everything
+    finite, and exactly 0 where A = 0 and on the ring."""
+    im1, im2, _ = RC.image_family(family, shape, 40 + shape[2])
+    go = RC.grad_out(shape, 41 + shape[2])
+    out = RC.forward(im1, im2, md, scale, normalize)
+    g1, g2, A = RC.backward(im1, im2, go, md, scale, normalize)
+    assert np.isfinite(out).all() and np.isfinite(g1).all() and np.isfinite(g2).all() and np.isfinite(A).all()
+    o, e1, e2 = RC.emulate(im1, im2, go, md, scale, normalize, mutate)
+    assert np.isfinite(o).all() and np.isfinite(e1).all() and np.isfinite(e2).all()
+    ring = ~RC.inner(shape[2], shape[3], md)
+    assert (o[:, 0][:, ring] == 0).all() and (e1[A == 0] == 0).all() and (e2[A == 0] == 0).all()
+    gb = RC.backward_bound(A)
+    pos = gb > 0
+    return (float(np.abs(o - out).max() / RC.forward_bound(md, normalize)), float((np.abs(e1 - g1)[pos] / gb[pos]).max()),
+            float((np.abs(e2 - g2)[pos] / gb[pos]).max()))
+
+
+def test_image_families_keep_their_conditions():
+    """Every family asserts in ``image_family`` what it is for; ``noise`` is the pair the other tests use; a family made benign
+    is refused."""
+    for shape in _FAMILY_SHAPES:
+        for name in RC.FAMILIES:
+            im1, im2, scale = RC.image_family(name, shape, 9)
+            assert im1.shape == im2.shape == shape and scale == (1.0 if name == "graded" else 255.0)
+        a, b, _ = RC.image_pair(shape, 9)
+        im1, im2, _ = RC.image_family("noise", shape, 9)
+        assert np.array_equal(a, im1) and np.array_equal(b, im2)
+    assert {f for f, _ in RC.FAMILY_SCALES} == set(RC.FAMILIES)
+    assert {s for f, s in RC.FAMILY_SCALES if f == "noise"} == {255.0, -255.0, 1.0, 2.0 ** -30}
+    assert {s for f, s in RC.FAMILY_SCALES if f == "seams"} == {255.0, 1.0}
+    # the conditions bite: each family's check on another family's images
+    shape = _FAMILY_SHAPES[1]
+    noise1, noise2, _ = RC.image_pair(shape, 9)
+    for md in (3,):
+        x1 = RC._taps(RC.grey(noise1, 255.0), md)
+        assert (np.abs(x1) < 1.75).mean() < 0.5                                     # knee's
+        d = RC.f(x1) - RC.f(RC._taps(RC.grey(noise2, 255.0), md))
+        assert np.median(np.abs(d)) < 1.5                                           # opposed's
+        assert RC.forward(noise1, noise2, md).max() > 1e-5                          # flat's
+        assert np.abs(RC.grey(noise1, 1.0)).max() < 2.0 ** 57                       # graded's
+
+
+def test_emulation_stays_inside_the_bounds_on_every_family():
+    """The float32 emulation of the header's operation list stays inside the header's bounds, in full, on every family and scale;
+    the worst error / bound per family is printed."""
+    for family, scale in RC.FAMILY_SCALES:
+        worst = np.zeros(3)
+        for shape in _FAMILY_SHAPES:
+            for md, normalize in _FAMILY_CONFIGS:
+                worst = np.maximum(worst, _emulated_ratios(shape, family, scale, md, normalize))
+        print(f"emulation, {family} at scale {scale:g}: forward {worst[0]:.4f}, grad_im1 {worst[1]:.4f}, grad_im2 {worst[2]:.4f}")
+        assert worst.max() <= 1.0, (family, scale, worst)
+
+
+@pytest.mark.parametrize("mutate,family,scale", [("abs_scale", "noise", -255.0), ("clamped_grey", "graded", 1.0), ("clamped_grey", "seams", 1.0)])
+def test_a_planted_mistake_passes_the_original_family_and_fails_a_new_one(mutate, family, scale):
+    """Teeth: a gradient scaled by |scale| and a grey intensity clamped to [0, 255] stay inside a quarter of the bounds on the
+    original pair at scale 255 -- and leave the bounds on the negative scale, the graded magnitudes and the +-1 checkerboard."""
+    shape, md, normalize = _FAMILY_SHAPES[1], 3, True
+    assert max(_emulated_ratios(shape, "noise", 255.0, md, normalize, mutate)) <= 0.25
+    bad, clean = _emulated_ratios(shape, family, scale, md, normalize, mutate), _emulated_ratios(shape, family, scale, md, normalize)
+    print(f"{mutate} on {family} at scale {scale:g}: error / bound {max(bad):.3g}, without the mistake {max(clean):.4f}")
+    assert max(bad) > 1 and max(clean) <= 1

@@ -338,3 +338,74 @@ def test_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
         assert scratch == 0, f"{name} spills {scratch} bytes per lane"
         want = patch if "splat_fwd_tiled" in name else 16 if "splat_plane_max" in name else 0
         assert int(lds) == want, f"{name} uses {lds} bytes of LDS, expected {want}"
+
+
+# ------------------------------------------------------------------ the input families
+_FAMILY_SHAPES = ((1, 2, 17, 67), (2, 5, 33, 130))
+
+
+def _ratio(err, bound):
+    return float((np.abs(err) / bound).max())
+
+
+def test_input_families_keep_their_conditions():
+    """Every family asserts in ``input_family`` what it is for, at both shapes the GPU tests use; the standard normal input
+    meets none of the conditions of ``cancel``, ``subnormal`` and ``huge``."""
+    for shape in _FAMILY_SHAPES:
+        B, C, H, W = shape
+        for name in RS.INPUT_FAMILIES:
+            inp, go = RS.input_family(name, shape, 5)
+            assert inp.shape == go.shape == shape and inp.dtype == go.dtype == np.float32
+            assert set(RS.FAMILY_FLOWS[name]) <= {"smooth", "converge", "shift", "zero"}
+        inp, _ = RS.input_family("normal", shape, 5)
+        out, S, n = RS.forward(inp, RS.flow_family("converge", B, H, W))
+        full = n == H * W
+        assert full.any() and not (np.abs(out[full]) <= 2.0 ** -6 * S[full]).all()
+        assert np.abs(inp).min() > 2.0 ** -120 and np.abs(inp).max() < 2.0 ** 125
+    graded, go = RS.input_family("graded", _FAMILY_SHAPES[1], 5)
+    tops = np.log2(np.abs(graded.astype(np.float64)).max(axis=(2, 3))).ravel()
+    assert all(abs(t - e) < 3 for t, e in zip(tops, RS.GRADED_EXPONENTS * 2))
+    assert "converge" not in RS.FAMILY_FLOWS["huge"]
+
+
+def test_emulation_stays_inside_the_bounds_on_every_family():
+    """The atomic forward and both gradients, emulated in numpy float32 from the header's operation list, stay inside the
+    header's bounds on every input family and flow, and the fixed-point result inside the forward bound plus 2^(K - 62) M per
+    contribution; the worst error / bound per family is printed.  The gradients of ``huge`` overflow and are not asked for."""
+    m = RS.header_macros()
+    for name in RS.INPUT_FAMILIES:
+        worst = np.zeros(4)
+        for shape in _FAMILY_SHAPES:
+            B, C, H, W = shape
+            inp, go = RS.input_family(name, shape, 50 + H)
+            for fl in RS.FAMILY_FLOWS[name]:
+                flow = RS.flow_family(fl, B, H, W)
+                out, S, n = RS.forward(inp, flow)
+                r = [_ratio(RS.emulate_forward(inp, flow) - out, RS.forward_bound(S, n)), _ratio(RS.forward_fixed(inp, flow) - out, RS.fixed_bound(inp, S, n)), 0, 0]
+                if name != "huge":
+                    (gi, Si), (gf, Sf) = RS.backward(inp, flow, go)
+                    egi, egf = RS.emulate_backward(inp, flow, go)
+                    r[2] = _ratio(egi - gi, m["FN2S_K_I"] * (RS.U23 * Si + RS.SUB))
+                    r[3] = _ratio(egf - gf, (C + m["FN2S_K_F"]) * (RS.U23 * Sf + RS.SUB))
+                worst = np.maximum(worst, r)
+        print(f"emulation, {name}: forward {worst[0]:.3f}, fixed point {worst[1]:.3f}, grad_input {worst[2]:.3f}, grad_flow {worst[3]:.3f}")
+        assert worst.max() <= 1.0, (name, worst)
+
+
+def test_planted_mistakes_pass_the_normal_input_and_fail_a_new_family():
+    """Teeth.  An addition that flushes a subnormal sum to 0 stays inside the forward bound on the standard normal input and
+    leaves it on ``subnormal``; a fixed-point scaling done in float32 (2^s a float32 of its own) gives the contract's bits on the
+    standard normal input, where s is about 47, and not on ``graded`` (s = 150 for the plane of 2^-100) nor on ``subnormal``."""
+    shape = _FAMILY_SHAPES[0]
+    B, C, H, W = shape
+    flow = RS.flow_family("smooth", B, H, W)
+    seen = {}
+    for name in ("normal", "subnormal", "graded"):
+        inp, _ = RS.input_family(name, shape, 50 + H)
+        out, S, n = RS.forward(inp, flow)
+        if name != "graded":
+            seen[name, "ftz_add"] = _ratio(RS.emulate_forward(inp, flow, "ftz_add") - out, RS.forward_bound(S, n))
+        seen[name, "float_scale"] = bool((RS.forward_fixed(inp, flow, "float_scale").view(np.uint32) == RS.forward_fixed(inp, flow).view(np.uint32)).all())
+    print(seen)
+    assert seen["normal", "ftz_add"] <= 1.0 < seen["subnormal", "ftz_add"]
+    assert seen["normal", "float_scale"] and not seen["graded", "float_scale"] and not seen["subnormal", "float_scale"]

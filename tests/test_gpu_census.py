@@ -9,7 +9,9 @@ Shapes (N, C, H, W): (1, 1, 1, 1); (1, 1, 7, 7), where max_distance 3 leaves exa
 max_distance 3 leaves nothing; (1, 1, 17, 67), ragged against the FN2C_TILE_H x FN2C_TILE_W = 16 x 64 tile both ways;
 (2, 3, 33, 130), several tiles both ways, so halos cross tile seams.  Each with max_distance 1, 2, 3 and normalize on and off.
 Inputs: census_ref.image_pair -- im1 uniform, im2 = im1 + 5 % noise -- on which the fp32 PyTorch composition itself stays below
-0.03 of the bounds, so a quarter of the bound is far from the reference's own error.
+0.03 of the bounds, so a quarter of the bound is far from the reference's own error.  At the two larger shapes also
+census_ref.image_family's families at their scales -- low contrast, opposed images, a flat pair, graded magnitudes, transitions on
+the tile seams, negative, unit and tiny scales -- against the bounds in full.
 """
 from functools import lru_cache
 
@@ -314,8 +316,82 @@ def test_census_loss_matches_its_composition(dev):
         CensusLoss(3)(a, b, mask[:, :, 1:])
 
 
+# ------------------------------------------------------------------ 5. the image families, against the bounds in full
+FAMILY_SHAPES = [SHAPES[3], SHAPES[4]]
+FAMILY_MDS = (1, 3)
+FAMILY_RATIOS = {}   # (family, scale, quantity) -> largest error / bound seen
+
+
+@lru_cache(maxsize=None)
+def _family_inputs(shape, family):
+    seed = 1000 * shape[2] + 10 * shape[3] + shape[1] + 7 * RC.FAMILIES.index(family)
+    im1, im2, _ = RC.image_family(family, shape, seed)
+    go = RC.grad_out(shape, seed + 1)
+    for a in (im1, im2, go):
+        a.setflags(write=False)
+    return im1, im2, go
+
+
+def _inside(got, ref, bound, key, what):
+    """err <= bound per element, the header's bound with factor 1; finite; where the bound is 0 the value is exactly 0."""
+    got = got.detach().cpu().numpy().astype(np.float64)
+    assert np.isfinite(got).all(), f"{what}: not finite"
+    err = np.abs(got - ref)
+    bound = np.broadcast_to(np.asarray(bound, np.float64), err.shape)
+    zero = bound == 0
+    ratio = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
+    FAMILY_RATIOS[key] = max(FAMILY_RATIOS.get(key, 0.0), ratio)
+    print(f"{what}: largest error / bound {ratio:.4f}")
+    assert (got[zero] == 0).all(), f"{what}: not exactly 0 where the bound is 0"
+    if not ratio <= 1.0:
+        i = np.unravel_index(np.argmax(np.where(zero, 0, err / np.where(zero, 1, bound))), err.shape)
+        raise AssertionError(f"{what}: error {err[i]:.3e} > the bound {bound[i]:.3e} at {i} (ratio {ratio:.3f}): got {got[i]!r}, want {ref[i]!r}")
+
+
+@pytest.mark.parametrize("family,scale", RC.FAMILY_SCALES, ids=lambda v: v if isinstance(v, str) else f"{v:g}")
+@pytest.mark.parametrize("shape", FAMILY_SHAPES, **_ids)
+def test_image_families_within_the_bounds(dev, shape, family, scale):
+    """Every family of census_ref (each asserts its own condition when it is drawn) at its scales, max_distance 1 and 3, normalize
+    on and off: the forward inside 2^-19 w K and both gradients inside 2^-15 A(q, c), factor 1; finite everywhere; exactly +0 on the
+    ring and exactly 0 where A = 0; the repeated run bit for bit."""
+    N, C, H, W = shape
+    im1, im2, go = _family_inputs(shape, family)
+    a, b, g = (torch.tensor(v, device=dev) for v in (im1, im2, go))
+    for md in FAMILY_MDS:
+        ring = torch.from_numpy(~RC.inner(H, W, md)).to(dev)
+        for normalize in (True, False):
+            what = f"{family} scale {scale:g} {shape} md {md} normalize {normalize}"
+            ref = RC.forward(im1, im2, md, scale, normalize)
+            r1, r2, A = RC.backward(im1, im2, go, md, scale, normalize)
+            assert np.isfinite(ref).all() and np.isfinite(r1).all() and np.isfinite(r2).all() and np.isfinite(A).all()
+            outs = []
+            for _ in range(2):
+                out, whole = _guarded((N, 1, H, W), dev)
+                fn2_capi.census_forward(a, b, md, scale, normalize, out=out)
+                g1, w1 = _guarded(shape, dev)
+                g2, w2 = _guarded(shape, dev)
+                fn2_capi.census_backward(a, b, g, md, scale, normalize, True, True, grads=(g1, g2))
+                torch.cuda.synchronize()
+                for view, buf, name in ((out, whole, "forward"), (g1, w1, "grad_im1"), (g2, w2, "grad_im2")):
+                    _untouched(buf, view, f"{name} {what}")
+                outs.append((out, g1, g2))
+            (out, g1, g2), again = outs
+            for x, y, name in zip(outs[0], again, ("forward", "grad_im1", "grad_im2")):
+                _same_bits(y, x, f"{name} {what}: two runs differ")
+            _inside(out, ref, RC.forward_bound(md, normalize), (family, scale, "forward"), "forward " + what)
+            assert bool((_bits(out)[:, 0][:, ring] == 0).all()), f"{what}: the border ring is not +0"
+            bound = RC.backward_bound(A)
+            assert (bound > 0).any()
+            _inside(g1, r1, bound, (family, scale, "grad_im1"), "grad_im1 " + what)
+            _inside(g2, r2, bound, (family, scale, "grad_im2"), "grad_im2 " + what)
+
+
 def test_report_largest_ratios():
     """Last: the largest error / bound ratios of this run, for DESIGN 4.14."""
     for key in sorted(RATIOS):
         print("largest error / bound", key, f"{RATIOS[key]:.4f}")
+    for family, scale, quantity in sorted(FAMILY_RATIOS):
+        print("largest error / bound, family", family, f"scale {scale:g}", quantity, f"{FAMILY_RATIOS[family, scale, quantity]:.4f}")
     assert set(RATIOS) == {"forward", "grad_im1", "grad_im2"} and max(RATIOS.values()) <= 0.25
+    assert set(FAMILY_RATIOS) == {(f, s, q) for f, s in RC.FAMILY_SCALES for q in ("forward", "grad_im1", "grad_im2")}
+    assert max(FAMILY_RATIOS.values()) <= 1.0

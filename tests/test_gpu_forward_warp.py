@@ -9,7 +9,8 @@ forward has to clear its output itself.
 Shapes (B, C, H, W): (1, 1, 1, 1), (2, 3, 5, 7), (1, 2, 17, 67), (2, 5, 33, 130) -- one pixel, less than a wave, ragged against
 the FN2S_TILE_H x FN2S_TILE_W = 16 x 64 tile in both directions, and several tiles in both directions with C = 5 against the
 channel group of 2.  Flow families (forward_warp_ref.flow_family): smooth, random, converge, zero, shift; each test asserts on
-its own input that the family still exercises its branch.
+its own input that the family still exercises its branch.  Inputs: standard normal there; at the two larger shapes also
+forward_warp_ref.input_family's graded, cancelling, subnormal and huge planes, each under the flows it is meant for.
 """
 from functools import lru_cache
 
@@ -418,6 +419,66 @@ def test_softsplat_modes_and_range_map(dev):
         out = forward_warp_cuda.forward_alloc(*_dev(cs, dev, "inp", "flow"))
     side.synchronize()
     _within(out, cs["out"], cs["bound"], ("forward", "module"), "forward on a side stream, device 0 selected")
+
+
+# ------------------------------------------------------------------ 10. the input families
+NEW_INPUTS = [f for f in RS.INPUT_FAMILIES if f != "normal"]
+
+
+@lru_cache(maxsize=None)
+def _family_case(shape, family, flow_name):
+    """One (shape, input family, flow family): inputs and references, computed once and shared; the arrays are read-only.  The
+    input family asserts its own condition when it is drawn."""
+    B, C, H, W = shape
+    inp, go = RS.input_family(family, shape, 1000 * H + 10 * W + 50 + RS.INPUT_FAMILIES.index(family))
+    flow = RS.flow_family(flow_name, B, H, W)
+    out, S, n = RS.forward(inp, flow)
+    case = dict(inp=inp, go=go, flow=flow, out=out, S=S, n=n, bound=RS.forward_bound(S, n), fixed=RS.forward_fixed(inp, flow))
+    if family != "huge":      # its gradients overflow
+        (case["gi"], case["Si"]), (case["gf"], case["Sf"]) = RS.backward(inp, flow, go)
+    for v in case.values():
+        v.setflags(write=False)
+    return case
+
+
+@pytest.mark.parametrize("family", NEW_INPUTS)
+@pytest.mark.parametrize("shape", LARGE, ids=lambda s: "x".join(map(str, s)))
+def test_input_families_forward_within_the_bound(dev, shape, family):
+    """Graded, cancelling, subnormal and huge inputs under the flows they are meant for: every variant inside the header's
+    forward bound per cell -- its floor is (n + 2) 2^-149, so a subnormal sum has to survive the atomics --, a cell nothing lands
+    on +0, and the deterministic entry point the bits of the fixed-point contract, for plane maxima from 2^-127 to 2^126."""
+    for flow_name in RS.FAMILY_FLOWS[family]:
+        c = _family_case(shape, family, flow_name)
+        x, fl = _dev(c, dev, "inp", "flow")
+        empty = torch.from_numpy(c["S"] == 0).to(dev)
+        assert np.isfinite(c["out"]).all() and np.isfinite(c["bound"]).all()
+        for variant in VARIANTS:
+            what = f"{variant} {shape} {family} {flow_name}"
+            out, whole = _forward(variant, x, fl)
+            _untouched(whole, out, what)
+            _within(out, c["out"], c["bound"], ("forward " + family, variant), "forward " + what)
+            assert bool((_bits(out)[empty] == 0).all()), f"{what}: a cell without contributions is not +0"
+            if variant == "det":
+                _same_bits(out, c["fixed"], f"{what}: not the fixed-point result")
+
+
+@pytest.mark.parametrize("family", ["graded", "cancel", "subnormal"])
+@pytest.mark.parametrize("shape", LARGE, ids=lambda s: "x".join(map(str, s)))
+def test_input_families_backward_within_the_bounds(dev, shape, family):
+    """Both gradients inside the header's bounds on the graded, cancelling and subnormal inputs; two runs give the same bits."""
+    m = RS.header_macros()
+    KI, KF = m["FN2S_K_I"], m["FN2S_K_F"]
+    for flow_name in RS.FAMILY_FLOWS[family]:
+        c = _family_case(shape, family, flow_name)
+        x, fl, g = _dev(c, dev, "inp", "flow", "go")
+        what = f"{shape} {family} {flow_name}"
+        gi, gf = fn2_capi.forward_warp_backward(x, fl, g)
+        torch.cuda.synchronize()
+        _within(gi, c["gi"], KI * (U23 * c["Si"] + SUB), ("grad_input " + family, flow_name), "grad_input " + what)
+        _within(gf, c["gf"], (shape[1] + KF) * (U23 * c["Sf"] + SUB), ("grad_flow " + family, flow_name), "grad_flow " + what)
+        gi2, gf2 = fn2_capi.forward_warp_backward(x, fl, g)
+        _same_bits(gi2, gi, what + " grad_input: two runs differ")
+        _same_bits(gf2, gf, what + " grad_flow: two runs differ")
 
 
 def test_report_largest_ratios():

@@ -12,7 +12,9 @@ FN2M_TILE_H x FN2M_TILE_W tile, staged with 16-byte loads; (1, 1, 1, 17, 65), ra
 tiles both ways, so halos cross tile seams, staged one float at a time; (2, 3, 3, 20, 132), several tiles with 16-byte staging
 (W a multiple of 4).  Each with both orders, both edge weightings, eps 0.001 and 0.01 and both image families of smoothness_ref
 (alpha 150 on a 5 % image, alpha 10 on a 75 % image: e stays below about 56), on which the fp32 PyTorch composition itself stays
-below 0.29 of the bounds.
+below 0.29 of the bounds.  At the last three shapes also smoothness_ref.inputs' named families -- flushed weights, a ramp whose
+second difference cancels, a large offset, graded magnitudes, alpha = 0 -- against the header's bounds in full; the header's
+gradient bound is ``backward(..., corrected=True)``'s third array, the original tests keep the first-order bound it replaced.
 """
 from functools import lru_cache
 
@@ -367,8 +369,94 @@ def test_smoothness_loss_matches_its_composition(dev):
         _within(x.grad, gref, gb, "grad_flow", f"SmoothnessLoss gradient {shape}")
 
 
+# ------------------------------------------------------------------ 5. the named input families, against the bounds in full
+FAMILY_SHAPES = [SHAPES[5], SEAMS, SEAMS_VEC]
+FAMILY_RATIOS = {}   # (family, quantity) -> largest error / bound seen
+
+
+def _family_eps(family):
+    return RS.GRADED_EPS if family == "graded" else (0.0, 0.001)
+
+
+@lru_cache(maxsize=None)
+def _family_inputs(shape, family):
+    flow, image, go, alpha = RS.inputs(shape, family, 1000 * shape[3] + 10 * shape[4] + shape[1] + 7 * RS.NEW_FAMILIES.index(family))
+    for a in (flow, image, go):
+        a.setflags(write=False)
+    return flow, image, go, alpha
+
+
+def _inside(got, ref, bound, key, what):
+    """err <= bound per element, the header's bound with factor 1; where the bound is 0 the value is exactly 0."""
+    got = got.detach().cpu().numpy().astype(np.float64)
+    assert np.isfinite(bound).all(), f"{what}: the bound is not finite"
+    err = np.abs(got - ref)
+    zero = bound == 0
+    ratio = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
+    FAMILY_RATIOS[key] = max(FAMILY_RATIOS.get(key, 0.0), ratio)
+    print(f"{what}: largest error / bound {ratio:.4f}")
+    assert (got[zero] == 0).all(), f"{what}: not exactly 0 where the bound is 0"
+    if not ratio <= 1.0:
+        i = np.unravel_index(np.argmax(np.where(zero, 0, err / np.where(zero, 1, bound))), err.shape)
+        raise AssertionError(f"{what}: error {err[i]:.3e} > the bound {bound[i]:.3e} at {i} (ratio {ratio:.3f}): got {got[i]!r}, want {ref[i]!r}")
+
+
+def _dead_cells(shape, flow, image, order, edge, alpha):
+    """N x 2 x H x W bool: the cells whose edge measure is above 104, where exp2's argument is below -150."""
+    N, F, C, H, W = shape
+    dead = np.zeros((N, 2, H, W), bool)
+    for plane, axis in ((0, 3), (1, 2)):
+        q = RS._direction(flow, image, axis, order, edge, alpha, 0.0)
+        L = (H, W)[axis - 2]
+        dead[(slice(None), slice(plane, plane + 1)) + RS._sl(axis, 0, L - order)[2:]] = q["e"] > 104
+    return dead
+
+
+@pytest.mark.parametrize("family", RS.NEW_FAMILIES)
+@pytest.mark.parametrize("shape", FAMILY_SHAPES, **_ids)
+def test_input_families_within_the_bounds(dev, shape, family):
+    """Every named family of smoothness_ref (each asserts its own condition when it is drawn) with both orders and both
+    weightings: the forward inside the header's forward bound, the gradient inside the header's gradient bound, both with factor
+    1; cells without a term +0; two backward runs the same bits.  ``edges``: a cell with e > 104 is exactly +0 and gives the
+    gradient nothing, whatever its grad_out.  ``alpha0`` with eps = 0 on exactly representable flows: the float64 value, exactly."""
+    flow, image, go, alpha = _family_inputs(shape, family)
+    f, im, g = (torch.tensor(a, device=dev) for a in (flow, image, go))
+    for order in ORDERS:
+        for edge in RS.EDGES:
+            for eps in _family_eps(family):
+                what = f"{family} {shape} order {order} {edge} eps {eps:.3g}"
+                ref, fb = RS.forward(flow, image, order, edge, alpha, eps)
+                gref, _, gb = RS.backward(flow, image, go, order, edge, alpha, eps, corrected=True)
+                out, whole = _forward(f, im, order, edge, alpha, eps)
+                _untouched(whole, out, what)
+                _inside(out, ref, fb, (family, "forward"), "forward " + what)
+                assert bool((_bits(out)[_no_term(shape, order, dev)] == 0).all()), f"{what}: a cell without a term is not +0"
+                grad, whole = _backward(f, im, g, order, edge, alpha, eps)
+                _untouched(whole, grad, what)
+                _inside(grad, gref, gb, (family, "grad_flow"), "grad_flow " + what)
+                if eps == _family_eps(family)[-1]:
+                    again, _ = _backward(f, im, g, order, edge, alpha, eps)
+                    _same_bits(again, grad, what + ": two runs differ")
+                if family == "edges":
+                    dead = _dead_cells(shape, flow, image, order, edge, alpha)
+                    assert dead.any() and not dead.all()
+                    dead_d = torch.tensor(dead, device=dev)
+                    assert bool((_bits(out)[dead_d] == 0).all()), f"{what}: a cell with e > 104 is not +0"
+                    tripled, _ = _backward(f, im, torch.where(dead_d, 3 * g, g), order, edge, alpha, eps)
+                    _same_bits(tripled, grad, what + ": grad_out of a cell with e > 104 reaches the gradient")
+                    without, _ = _backward(f, im, torch.where(dead_d, torch.zeros_like(g), g), order, edge, alpha, eps)
+                    assert bool((without == grad).all()), f"{what}: a cell with e > 104 contributes to the gradient"
+                if family == "alpha0" and eps == 0.0:
+                    emu, _ = RS.emulate(flow, image, go, order, edge, alpha, eps)
+                    assert np.array_equal(emu.astype(np.float64), ref)      # every rho and their sum are exact
+                    _same_bits(out, torch.tensor(emu, device=dev), what + ": not sum_f rho exactly with alpha = 0")
+
+
 def test_report_largest_ratios():
     """Last: the largest error / bound ratios of this run, for DESIGN 4.15."""
     for key in sorted(RATIOS):
         print("largest error / bound", key, f"{RATIOS[key]:.4f}")
+    for family, quantity in sorted(FAMILY_RATIOS):
+        print("largest error / bound, family", family, quantity, f"{FAMILY_RATIOS[family, quantity]:.4f}")
     assert set(RATIOS) == {"forward", "grad_flow"} and max(RATIOS.values()) <= 0.5
+    assert set(FAMILY_RATIOS) == {(fam, q) for fam in RS.NEW_FAMILIES for q in ("forward", "grad_flow")} and max(FAMILY_RATIOS.values()) <= 1.0

@@ -409,3 +409,94 @@ def test_kernels_use_no_scratch_and_their_lds_is_the_headers_formula(tmp_path):
         seen.add((kind, k, C, F))
     assert seen == {(d, k, C, F) for d in ("fwd", "bwd") for k in (1, 2) for C in (1, 3) for F in (1, 2, 3, 4)}
     assert RS.lds_bytes(5, 2, False) == 24480 and RS.lds_bytes(9, 2, True) == 51840 <= 64 * 1024
+
+
+# ------------------------------------------------------------------ the input families and the corrected gradient bound
+_FAMILY_SHAPES = ((1, 1, 1, 17, 65), (2, 2, 3, 33, 130))
+
+
+def _family_eps(family):
+    return RS.GRADED_EPS if family == "graded" else (0.0, 0.001)
+
+
+def _worst(err, bound):
+    """Largest err / bound where the bound is positive; where it is 0 the error must be 0."""
+    assert (err[bound == 0] == 0).all()
+    pos = bound > 0
+    return float((err[pos] / bound[pos]).max()) if pos.any() else 0.0
+
+
+def _emulated_ratios(shape, family, order, edge, eps, mutate=None):
+    """(forward, gradient against the first-order bound, gradient against the corrected bound, corrected / first-order) of the
+    float32 emulation of the header's operation list."""
+    flow, image, go, alpha = RS.inputs(shape, family, 77 + shape[3])
+    out, fb = RS.forward(flow, image, order, edge, alpha, eps)
+    grad, gb, gc = RS.backward(flow, image, go, order, edge, alpha, eps, corrected=True)
+    assert np.isfinite(fb).all() and np.isfinite(gc).all() and (gc >= gb).all(), "(a): the corrected bound is below the first-order one"
+    o, g = RS.emulate(flow, image, go, order, edge, alpha, eps, mutate)
+    eg = np.abs(g.astype(np.float64) - grad)
+    old = float((eg / np.where(gb > 0, gb, 2.0 ** -1074)).max())
+    grow = float((gc[gb > 0] / gb[gb > 0]).max()) if (gb > 0).any() else 1.0
+    return _worst(np.abs(o.astype(np.float64) - out), fb), old, _worst(eg, gc), grow
+
+
+def test_input_families_keep_their_conditions():
+    """Every named family asserts in ``inputs`` what it is for; here at every shape the GPU tests use, and a family made benign
+    is refused."""
+    for shape in _FAMILY_SHAPES + ((2, 3, 3, 20, 132),):
+        for family in RS.NEW_FAMILIES:
+            flow, image, go, alpha = RS.inputs(shape, family, 3)
+            assert flow.dtype == image.dtype == go.dtype == np.float32 and flow.shape == shape[:2] + shape[3:]
+    flow, image, go, alpha = RS.inputs(_FAMILY_SHAPES[1], "ramp", 3)
+    plain = RS.inputs(_FAMILY_SHAPES[1], 0, 3)[0]
+    for family, bad in (("ramp", plain), ("offset", plain), ("graded", plain)):
+        with pytest.raises(AssertionError):
+            RS.check_family(family, bad, image, alpha)
+    with pytest.raises(AssertionError):
+        RS.check_family("edges", flow, np.full_like(image, 0.5), alpha)
+    with pytest.raises(AssertionError):
+        RS.check_family("alpha0", flow, image, 150.0)
+
+
+def test_emulation_stays_inside_the_corrected_bound_and_leaves_the_first_order_one_on_ramp():
+    """(a) the corrected gradient bound is nowhere below the first-order one of ABI 1; (b) on the two original families it
+    exceeds it by at most 1.1 (printed); (c) the float32 emulation of the header's list stays inside the forward
+    bound and the corrected gradient bound on every family and every (order, edge, eps); (d) on ``ramp`` with order 2 it
+    exceeds the first-order bound -- by 10^5 at eps = 0 -- which is why the header changed."""
+    grow_old, left = 1.0, {}
+    for family in (0, 1) + RS.NEW_FAMILIES:
+        worst = [0.0, 0.0, 0.0]
+        for shape in _FAMILY_SHAPES:
+            for order in (1, 2):
+                for edge in RS.EDGES:
+                    for eps in ((0.001, 0.01) if family in (0, 1) else _family_eps(family)):
+                        f, old, new, grow = _emulated_ratios(shape, family, order, edge, eps)
+                        worst = [max(a, b) for a, b in zip(worst, (f, old, new))]
+                        if family in (0, 1):
+                            grow_old = max(grow_old, grow)
+                        if family == "ramp" and order == 2:
+                            left[eps] = max(left.get(eps, 0.0), old)
+        print(f"emulation, family {family}: forward {worst[0]:.3f}, gradient / first-order bound {worst[1]:.3g}, / corrected bound {worst[2]:.3f}")
+        assert worst[0] <= 1 and worst[2] <= 1, (family, worst)
+        if family in (0, 1):
+            assert worst[1] <= 0.5
+    print(f"corrected / first-order gradient bound on the original families: at most {grow_old:.3f}")
+    assert 1.0 <= grow_old <= 1.1
+    print("ramp, order 2: emulation / first-order bound", {k: f"{v:.3g}" for k, v in left.items()})
+    assert left[0.0] > 1e4 and left[0.001] > 10
+
+
+@pytest.mark.parametrize("mutate,family,order,eps", [("d2_regrouped", "offset", 2, 0.001), ("clamped_exponent", "edges", 1, 0.001)])
+def test_a_planted_mistake_passes_the_original_families_and_fails_a_new_one(mutate, family, order, eps):
+    """Teeth, on the forward: the second difference regrouped as (f[x + 2] - 2 f[x + 1]) + f[x] and exp2's argument clamped
+    at -125 (no weight is flushed) stay inside half of the forward bound on both original families -- and leave it on ``offset`` and on
+    ``edges``, where the unchanged emulation stays inside."""
+    shape = _FAMILY_SHAPES[1]
+    for old in (0, 1):
+        for edge in RS.EDGES:
+            f = _emulated_ratios(shape, old, order, edge, eps, mutate)[0]
+            assert f <= 0.5, (old, edge, f)
+    f = _emulated_ratios(shape, family, order, "exponential", eps, mutate)[0]
+    clean = _emulated_ratios(shape, family, order, "exponential", eps)[0]
+    print(f"{mutate} on {family}: forward error / bound {f:.3g}, without the mistake {clean:.3f}")
+    assert f > 1 and clean <= 1
