@@ -1,5 +1,12 @@
 // capi.hip -- C-ABI entry points of libflownet2_hip.so that are not tied to one kernel file:
 // error strings, shape math and the correlation dispatcher (include/flownet2_hip.h).
+//
+// The dispatcher is the table kCorrRows below: one row per kernel -- the algo values that select it, its domain and its launcher
+// per direction, the alignment the dispatcher itself asks for -- in the order FN2_CORR_AUTO tries them.  corr_plan lists the rows
+// a call selects that admit it (domain, alignment; forward: the batch stride's divisor and AUTO's gate), corr_dispatch runs them.
+// FN2_CORR_AUTO goes on to the next row when a launcher declines (FN2_EUNSUPPORTED / FN2_EALIGN, nothing launched).  Any other algo
+// plans the first admitted row it selects and returns that launcher's code as it is, or FN2_EUNSUPPORTED if there is none.  A debug
+// variant (fn2_debug.h) names its row: 9000 DENSE, forward >= 5000 / backward >= 6000 F16X2, every other value MFMA_F32.
 #include <math.h>
 
 #include "corr_params.h"
@@ -41,80 +48,99 @@ extern "C" int fn2_correlation_output_shape(int H, int W, int pad_size, int kern
     return FN2_OK;
 }
 
-static int corr_forward_impl(const void *in1, const void *in2, void *out, int64_t out_batch_stride,
-                             float negative_slope, int dtype, int B, int C, int H, int W,
-                             int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
-                             int algo, bool debug_variant, void *stream)
+namespace fn2 {
+namespace {
+
+enum { FWD = 0, BWD = 1 };
+struct CorrRow {                       // kCorrRows[FN2_CORR_KERNEL_x] (fn2_debug.h) is the row of kernel x
+    unsigned algos;                    // bit a: algo a selects the row
+    CorrPredicate *domain[2];          // [FWD], [BWD]; null: every call
+    CorrLauncher *launch[2];
+    int align[2], out_bs_div;          // bytes in1, in2 and out / grad_out must be aligned to (0: no rule here); forward: divisor of out_batch_stride
+    bool align_grads;                  // backward: grad_in1 and grad_in2 as well
+    bool (*auto_gate)(const CorrP &);  // forward under FN2_CORR_AUTO only: is the kernel worth taking?
+};
+#define FN2_ALGO(a) (1u << FN2_CORR_##a)
+constexpr CorrRow kCorrRows[FN2_CORR_KERNEL_COUNT] = {
+    /* H16 */ {FN2_ALGO(AUTO) | FN2_ALGO(MFMA_F16X2), {corr_f16_fwd_applicable, corr_f16_bwd_applicable},
+               {corr_forward_f16, corr_backward_f16}, {0, 0}, 1, false, nullptr},
+    /* F16X2 */ {FN2_ALGO(AUTO) | FN2_ALGO(MFMA_F16X2), {corr_f16x2_applicable, corr_bwd_f16x2_applicable},
+                 {corr_forward_f16x2, corr_backward_f16x2}, {16, 16}, 4, true, nullptr},
+    /* MFMA_F32 */ {FN2_ALGO(AUTO) | FN2_ALGO(MFMA_F32) | FN2_ALGO(MFMA_BF16X3), {corr_mfma_f32_applicable, corr_bwd_mfma_f32_applicable},
+                    {corr_forward_mfma_f32, corr_backward_mfma_f32}, {8, 8}, 2, false, nullptr},
+    /* F64 */ {FN2_ALGO(AUTO), {corr_mfma_f64_applicable, corr_mfma_f64_applicable},
+               {corr_forward_mfma_f64, corr_backward_mfma_f64}, {16, 16}, 2, false, nullptr},
+    /* DENSE */ {FN2_ALGO(AUTO), {corr_dense_applicable, corr_dense_applicable},
+                 {corr_forward_dense, corr_backward_dense}, {0, 0}, 1, false, corr_dense_forward_pays},
+    /* DIRECT */ {FN2_ALGO(AUTO) | FN2_ALGO(DIRECT), {nullptr, nullptr}, {corr_forward_direct, corr_backward_direct}, {0, 0}, 1, false, nullptr},
+};
+#undef FN2_ALGO
+
+// How many rows corr_dispatch would try (the first `max` in ids[]; 0: an empty batch), or the code the call ends with before any launch
+int corr_plan(int dir, const CorrCall &c, int algo, bool debug_variant, int *ids, int max)
 {
-    using namespace fn2;
-    const size_t es = dtype_size(dtype);
-    if (!es) return FN2_EDTYPE;
-    CorrP p;
-    int rc = corr_make_params(p, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
-    if (rc != FN2_OK) return rc;
-    if (out_batch_stride < p.out_bs || !(negative_slope == negative_slope)) return FN2_EINVAL;
-    p.out_bs = out_batch_stride;
-    p.slope = negative_slope;
-    if (B == 0) return FN2_OK;
-    if (!in1 || !in2 || !out) return FN2_EINVAL;
-    if (!aligned(in1, es) || !aligned(in2, es) || !aligned(out, es)) return FN2_EALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const void *ptrs[5] = {c.in1, c.in2, dir == FWD ? c.out : c.gout, c.g1, c.g2};
+    const int nptrs = dir == FWD ? 3 : 5;
+    if (c.p.B == 0) return 0;
+    for (int i = 0; i < nptrs; ++i) if (!ptrs[i]) return FN2_EINVAL;
+    for (int i = 0; i < nptrs; ++i) if (!aligned(ptrs[i], dtype_size(c.dtype))) return FN2_EALIGN;
     // profiling instantiations (wrong or partial outputs by design) are only reachable through fn2_debug_* (fn2_debug.h)
     if (!debug_variant && (algo < FN2_CORR_AUTO || algo > FN2_CORR_MFMA_F16X2)) return FN2_EINVAL;
-    // f16x2: two-term f16 split done once per staged value, 3 MFMAs per block product (correlation_f16x2.hip)
-    const bool f16x2_ok = corr_f16x2_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
-                          aligned(in1, 16) && aligned(in2, 16) && aligned(out, 16) && (out_batch_stride % 4 == 0);
-    // the dense stride-1 kernels by name (fn2_debug.h; correct results): decided before anything is launched
-    if (debug_variant && algo == FN2_DEBUG_CORR_DENSE) return corr_forward_dense(in1, in2, out, dtype, p, s);
-    if (debug_variant && algo >= 5000) {
-        if (!f16x2_ok) return FN2_EUNSUPPORTED;
-        return corr_forward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<float *>(out),
-                                  p.out_bs, p.slope, B, C, H, W, algo - 5000, s);
+    const bool walk = !debug_variant && algo == FN2_CORR_AUTO;
+    const int named = algo == FN2_DEBUG_CORR_DENSE ? FN2_CORR_KERNEL_DENSE   // a debug variant names its row
+                      : algo >= (dir == FWD ? 5000 : 6000) ? FN2_CORR_KERNEL_F16X2 : FN2_CORR_KERNEL_MFMA_F32;
+    int n = 0;
+    for (int id = 0; id < FN2_CORR_KERNEL_COUNT && (walk || n == 0); ++id) {
+        const CorrRow &r = kCorrRows[id];
+        const size_t a = r.align[dir];
+        if (debug_variant ? id != named : !((r.algos >> algo) & 1)) continue;
+        if (r.domain[dir] && !r.domain[dir](c.dtype, c.p)) continue;
+        if (a && !(aligned(ptrs[0], a) && aligned(ptrs[1], a) && aligned(ptrs[2], a))) continue;
+        if (a && dir == BWD && r.align_grads && !(aligned(c.g1, a) && aligned(c.g2, a))) continue;
+        if (dir == FWD && (c.p.out_bs % r.out_bs_div != 0 || (walk && r.auto_gate && !r.auto_gate(c.p)))) continue;
+        if (n < max) ids[n] = id;
+        ++n;
     }
-    // half / bfloat16 tensors on FlowNetC's configuration: the single-product 16-bit kernel (correlation_f16_fwd.hip); AUTO or the
-    // f16x2 selector
-    if (!debug_variant && (algo == FN2_CORR_AUTO || algo == FN2_CORR_MFMA_F16X2) &&
-        corr_f16_fwd_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
-        rc = corr_forward_f16(dtype, in1, in2, out, p.out_bs, p.slope, B, C, H, W, s);
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
+    return n ? n : FN2_EUNSUPPORTED;
+}
+
+} // namespace
+
+int corr_dispatch(int dir, CorrCall &c, int algo, bool debug_variant, hipStream_t s)
+{
+    int ids[FN2_CORR_KERNEL_COUNT];
+    const int n = corr_plan(dir, c, algo, debug_variant, ids, FN2_CORR_KERNEL_COUNT);
+    int rc = n;   // <= 0: nothing to launch
+    // only FN2_CORR_AUTO plans more than one kernel: one that declines (task table / index limits; nothing launched) hands over
+    for (int i = 0; i < n && (i == 0 || rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN); ++i) {
+        // f16x2: its profiling switches.  fp32 MFMA forward: algo itself (0 auto, 2 fp32 MFMA, 3 bf16x3, >= 100 profiling instantiations);
+        // backward: 0 = automatic (bf16x3 where its extra preconditions hold), 6 = fp32 MFMA, 4 = bf16x3 or FN2_EUNSUPPORTED, algo - 100
+        c.tune = 0;
+        if (ids[i] == FN2_CORR_KERNEL_F16X2 && debug_variant) c.tune = algo - (dir == FWD ? 5000 : 6000);
+        if (ids[i] == FN2_CORR_KERNEL_MFMA_F32)
+            c.tune = dir == FWD ? algo : algo == FN2_CORR_MFMA_F32 ? 6 : algo == FN2_CORR_MFMA_BF16X3 ? 4 : debug_variant ? algo - 100 : 0;
+        rc = kCorrRows[ids[i]].launch[dir](c, s);
     }
-    if (algo == FN2_CORR_MFMA_F16X2 && !f16x2_ok) return FN2_EUNSUPPORTED;
-    if (algo == FN2_CORR_MFMA_F16X2 || (algo == FN2_CORR_AUTO && f16x2_ok)) {
-        rc = corr_forward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<float *>(out),
-                                p.out_bs, p.slope, B, C, H, W, 0, s);
-        // automatic selection: a shape the launcher declines (task table / index limits; nothing launched) goes on to the
-        // next kernel, as below
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
-    }
-    const bool mfma_ok = corr_mfma_f32_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1,
-                                                  stride2) && aligned(in1, 8) && aligned(in2, 8) && aligned(out, 8) &&
-                         (out_batch_stride % 2 == 0);
-    const bool wants_mfma = (algo == FN2_CORR_MFMA_F32 || algo == FN2_CORR_MFMA_BF16X3 || debug_variant);
-    if (wants_mfma && !mfma_ok) return FN2_EUNSUPPORTED;
-    if (wants_mfma || (algo == FN2_CORR_AUTO && mfma_ok)) {
-        rc = corr_forward_mfma_f32(static_cast<const float *>(in1), static_cast<const float *>(in2),
-                                   static_cast<float *>(out), p.out_bs, p.slope, B, C, H, W, max_displacement,
-                                   algo, s); // 0 auto, 2 fp32 MFMA, 3 bf16x3, >= 100 profiling instantiations (debug only)
-        // automatic selection: a shape the tiled kernels decline (nothing launched) goes to the general kernel
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
-    }
-    if (algo != FN2_CORR_AUTO && algo != FN2_CORR_DIRECT) return FN2_EINVAL;
-    // double tensors on FlowNetC's configuration: v_mfma_f64_16x16x4_f64 (correlation_mfma_f64.hip); AUTO only -- FN2_CORR_DIRECT
-    // keeps selecting the one-thread-per-output kernel
-    if (algo == FN2_CORR_AUTO && corr_mfma_f64_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
-        aligned(in1, 16) && aligned(in2, 16) && aligned(out, 16) && (out_batch_stride % 2 == 0)) {
-        rc = corr_forward_mfma_f64(static_cast<const double *>(in1), static_cast<const double *>(in2), static_cast<double *>(out), p.out_bs,
-                                   (double)p.slope, B, C, H, W, s);
-        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
-    }
-    // dense stride-1 cost volumes (correlation_dense.hip): the general kernel's bits, so AUTO may take them; FN2_CORR_DIRECT never
-    // does.  Maps with too few tiles to fill the chip stay on the general kernel, which is faster there (corr_dense_forward_pays)
-    if (algo == FN2_CORR_AUTO && corr_dense_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
-        corr_dense_forward_pays(p)) {
-        rc = corr_forward_dense(in1, in2, out, dtype, p, s);
-        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
-    }
-    return corr_forward_direct(in1, in2, out, dtype, p, s);
+    return rc;
+}
+
+} // namespace fn2
+
+// Every correlation entry point of this file: the argument checks in their order, then the walk -- or, with max_ids >= 0, its plan
+static int corr_impl(int dir, fn2::CorrCall c, int B, int C, int H, int W, int pad_size, int kernel_size, int max_displacement, int stride1,
+                     int stride2, int64_t out_batch_stride, float negative_slope, int algo, bool debug_variant, void *stream,
+                     int *ids = nullptr, int max_ids = -1)
+{
+    using namespace fn2;
+    if (!dtype_size(c.dtype)) return FN2_EDTYPE;
+    const int rc = corr_make_params(c.p, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
+    if (rc != FN2_OK) return rc;
+    // the reference's backward indexes (and writes) out of bounds for stride1 != 1 (SURVEY.md a7)
+    if (dir == BWD && stride1 != 1) return FN2_EUNSUPPORTED;
+    if (dir == FWD && (out_batch_stride < c.p.out_bs || !(negative_slope == negative_slope))) return FN2_EINVAL;
+    if (dir == FWD) { c.p.out_bs = out_batch_stride; c.p.slope = negative_slope; }
+    if (max_ids >= 0) return corr_plan(dir, c, algo, debug_variant, ids, max_ids);
+    return corr_dispatch(dir, c, algo, debug_variant, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fn2_correlation_forward_fused(const void *in1, const void *in2, void *out, int64_t out_batch_stride,
@@ -122,8 +148,8 @@ extern "C" int fn2_correlation_forward_fused(const void *in1, const void *in2, v
                                              int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                              int algo, void *stream)
 {
-    return corr_forward_impl(in1, in2, out, out_batch_stride, negative_slope, dtype, B, C, H, W, pad_size, kernel_size,
-                             max_displacement, stride1, stride2, algo, false, stream);
+    return corr_impl(fn2::FWD, {dtype, {}, in1, in2, nullptr, out, nullptr, nullptr, 0}, B, C, H, W, pad_size, kernel_size,
+                     max_displacement, stride1, stride2, out_batch_stride, negative_slope, algo, false, stream);
 }
 
 extern "C" int fn2_correlation_forward_ex(const void *in1, const void *in2, void *out, int dtype,
@@ -148,85 +174,14 @@ extern "C" int fn2_correlation_forward(const void *in1, const void *in2, void *o
                                       stride1, stride2, FN2_CORR_AUTO, stream);
 }
 
-static int corr_backward_impl(const void *in1, const void *in2, const void *grad_out,
-                              void *grad_in1, void *grad_in2, int dtype,
-                              int B, int C, int H, int W,
-                              int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
-                              int algo, bool debug_variant, void *stream)
-{
-    using namespace fn2;
-    const size_t es = dtype_size(dtype);
-    if (!es) return FN2_EDTYPE;
-    CorrP p;
-    int rc = corr_make_params(p, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
-    if (rc != FN2_OK) return rc;
-    // the reference's backward indexes (and writes) out of bounds for stride1 != 1 (SURVEY.md a7)
-    if (stride1 != 1) return FN2_EUNSUPPORTED;
-    if (B == 0) return FN2_OK;
-    if (!in1 || !in2 || !grad_out || !grad_in1 || !grad_in2) return FN2_EINVAL;
-    if (!aligned(in1, es) || !aligned(in2, es) || !aligned(grad_out, es) || !aligned(grad_in1, es) ||
-        !aligned(grad_in2, es))
-        return FN2_EALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!debug_variant && (algo < FN2_CORR_AUTO || algo > FN2_CORR_MFMA_F16X2)) return FN2_EINVAL;
-    // f16x2: one-time two-term f16 split, gathered G operand (correlation_f16x2_bwd.hip)
-    const bool f16x2_ok = corr_bwd_f16x2_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
-                          aligned(in1, 16) && aligned(in2, 16) && aligned(grad_out, 16) && aligned(grad_in1, 16) && aligned(grad_in2, 16);
-    if (debug_variant && algo == FN2_DEBUG_CORR_DENSE) return corr_backward_dense(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);
-    if (debug_variant && algo >= 6000) {
-        if (!f16x2_ok) return FN2_EUNSUPPORTED;
-        return corr_backward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<const float *>(grad_out),
-                                   static_cast<float *>(grad_in1), static_cast<float *>(grad_in2), B, C, H, W, algo - 6000, s);
-    }
-    // half / bfloat16 tensors on FlowNetC's configuration: the single-product 16-bit kernel (correlation_f16_bwd.hip); AUTO or the
-    // f16x2 selector
-    if (!debug_variant && (algo == FN2_CORR_AUTO || algo == FN2_CORR_MFMA_F16X2) &&
-        corr_f16_bwd_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
-        rc = corr_backward_f16(dtype, in1, in2, grad_out, grad_in1, grad_in2, B, C, H, W, s);
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
-    }
-    if (!debug_variant && algo == FN2_CORR_MFMA_F16X2 && !f16x2_ok) return FN2_EUNSUPPORTED;
-    if (!debug_variant && (algo == FN2_CORR_MFMA_F16X2 || (algo == FN2_CORR_AUTO && f16x2_ok))) {
-        rc = corr_backward_f16x2(static_cast<const float *>(in1), static_cast<const float *>(in2), static_cast<const float *>(grad_out),
-                                 static_cast<float *>(grad_in1), static_cast<float *>(grad_in2), B, C, H, W, 0, s);
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
-    }
-    const bool mfma_ok = corr_bwd_mfma_f32_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1,
-                                                      stride2) &&
-                         aligned(in1, 8) && aligned(in2, 8) && aligned(grad_out, 8);
-    const bool wants_mfma = (algo == FN2_CORR_MFMA_F32 || algo == FN2_CORR_MFMA_BF16X3 || debug_variant);
-    if (wants_mfma && !mfma_ok) return FN2_EUNSUPPORTED;
-    if (wants_mfma || (algo == FN2_CORR_AUTO && mfma_ok)) {
-        // internal tune: 0 = automatic (bf16x3 where its extra preconditions hold), 6 = fp32 MFMA, 4 = bf16x3 or
-        // FN2_EUNSUPPORTED, algo - 100 = profiling variants
-        const int tune = algo == FN2_CORR_MFMA_F32 ? 6 : algo == FN2_CORR_MFMA_BF16X3 ? 4 : debug_variant ? algo - 100 : 0;
-        rc = corr_backward_mfma_f32(static_cast<const float *>(in1), static_cast<const float *>(in2),
-                                    static_cast<const float *>(grad_out), static_cast<float *>(grad_in1),
-                                    static_cast<float *>(grad_in2), B, C, H, W, max_displacement, tune, s);
-        if (!(algo == FN2_CORR_AUTO && (rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN))) return rc;
-    }
-    if (algo != FN2_CORR_AUTO && algo != FN2_CORR_DIRECT) return FN2_EINVAL;
-    if (algo == FN2_CORR_AUTO && corr_mfma_f64_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2) &&
-        aligned(in1, 16) && aligned(in2, 16) && aligned(grad_out, 16)) {
-        rc = corr_backward_mfma_f64(static_cast<const double *>(in1), static_cast<const double *>(in2), static_cast<const double *>(grad_out),
-                                    static_cast<double *>(grad_in1), static_cast<double *>(grad_in2), B, C, H, W, s);
-        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
-    }
-    if (algo == FN2_CORR_AUTO && corr_dense_applicable(dtype, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)) {
-        rc = corr_backward_dense(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);
-        if (!(rc == FN2_EUNSUPPORTED || rc == FN2_EALIGN)) return rc;
-    }
-    return corr_backward_direct(in1, in2, grad_out, grad_in1, grad_in2, dtype, p, s);
-}
-
 extern "C" int fn2_correlation_backward_ex(const void *in1, const void *in2, const void *grad_out,
                                            void *grad_in1, void *grad_in2, int dtype,
                                            int B, int C, int H, int W,
                                            int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                            int algo, void *stream)
 {
-    return corr_backward_impl(in1, in2, grad_out, grad_in1, grad_in2, dtype, B, C, H, W, pad_size, kernel_size,
-                              max_displacement, stride1, stride2, algo, false, stream);
+    return corr_impl(fn2::BWD, {dtype, {}, in1, in2, grad_out, nullptr, grad_in1, grad_in2, 0}, B, C, H, W, pad_size, kernel_size,
+                     max_displacement, stride1, stride2, 0, 1.0f, algo, false, stream);
 }
 
 extern "C" int fn2_correlation_backward(const void *in1, const void *in2, const void *grad_out,
@@ -249,8 +204,8 @@ extern "C" int fn2_debug_correlation_forward(const void *in1, const void *in2, v
     int nOut = 0, oH = 0, oW = 0;
     const int rc = fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH, &oW);
     if (rc != FN2_OK) return rc;
-    return corr_forward_impl(in1, in2, out, (int64_t)nOut * oH * oW, 1.0f, dtype, B, C, H, W, pad_size, kernel_size,
-                             max_displacement, stride1, stride2, variant, true, stream);
+    return corr_impl(fn2::FWD, {dtype, {}, in1, in2, nullptr, out, nullptr, nullptr, 0}, B, C, H, W, pad_size, kernel_size,
+                     max_displacement, stride1, stride2, (int64_t)nOut * oH * oW, 1.0f, variant, true, stream);
 }
 
 extern "C" int fn2_debug_correlation_backward(const void *in1, const void *in2, const void *grad_out, void *grad_in1,
@@ -259,8 +214,23 @@ extern "C" int fn2_debug_correlation_backward(const void *in1, const void *in2, 
                                               void *stream)
 {
     if (variant < 100) return FN2_EINVAL;
-    return corr_backward_impl(in1, in2, grad_out, grad_in1, grad_in2, dtype, B, C, H, W, pad_size, kernel_size,
-                              max_displacement, stride1, stride2, variant, true, stream);
+    return corr_impl(fn2::BWD, {dtype, {}, in1, in2, grad_out, nullptr, grad_in1, grad_in2, 0}, B, C, H, W, pad_size, kernel_size,
+                     max_displacement, stride1, stride2, 0, 1.0f, variant, true, stream);
+}
+
+extern "C" int fn2_debug_correlation_plan(int direction, const void *in1, const void *in2, void *out, void *grad_in1, void *grad_in2,
+                                          int64_t out_batch_stride, int dtype, int B, int C, int H, int W, int pad_size, int kernel_size,
+                                          int max_displacement, int stride1, int stride2, int algo, int *ids, int max_ids)
+{
+    if ((direction != fn2::FWD && direction != fn2::BWD) || max_ids < 0 || (max_ids && !ids)) return FN2_EINVAL;
+    int nOut = 0, oH = 0, oW = 0;
+    if (direction == fn2::FWD && !out_batch_stride) {   // as fn2_correlation_forward_ex
+        const int rc = fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH, &oW);
+        if (rc != FN2_OK) return rc;
+        out_batch_stride = (int64_t)nOut * oH * oW;
+    }
+    return corr_impl(direction, {dtype, {}, in1, in2, out, out, grad_in1, grad_in2, 0}, B, C, H, W, pad_size, kernel_size, max_displacement,
+                     stride1, stride2, out_batch_stride, 1.0f, algo, algo >= 100, nullptr, ids, max_ids);
 }
 
 extern "C" void fn2_debug_set_buffer(void *device_ptr) { fn2::corr_f16x2_set_debug_buffer(device_ptr); }

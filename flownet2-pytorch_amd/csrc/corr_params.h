@@ -12,38 +12,46 @@ struct CorrP {
     float slope;               // LeakyReLU negative slope applied to the output (1 = none)
 };
 
+// One correlation call as the dispatcher (capi.hip) hands it to a launcher: the tensors of its direction (forward: in1, in2, out;
+// backward: in1, in2, gout, g1, g2) and the launcher's own tune / variant value (0 = the product kernel)
+struct CorrCall {
+    int dtype;
+    CorrP p;
+    const void *in1, *in2, *gout;
+    void *out, *g1, *g2;
+    int tune;
+};
+typedef bool CorrPredicate(int dtype, const CorrP &p);        // a kernel's domain: pure, no pointer is looked at
+typedef int CorrLauncher(const CorrCall &c, hipStream_t s);   // FN2_EUNSUPPORTED / FN2_EALIGN: declined, nothing launched
+
 int corr_make_params(CorrP &p, int B, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_direct(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s);
-int corr_backward_direct(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype,
-                         const CorrP &p, hipStream_t s);
+int corr_dispatch(int direction, CorrCall &c, int algo, bool debug_variant, hipStream_t s);   // capi.hip; direction 0 forward, 1 backward
+CorrLauncher corr_forward_direct, corr_backward_direct;
 
 // dense stride-1 cost volumes (PWC-Net: k = 1, s1 = s2 = 1, pad == md, 1 <= md <= 4; f32 / f16 / bf16; correlation_dense.hip): LDS-tiled
 // VALU kernels with the bits of corr_*_direct.  They decline (FN2_EUNSUPPORTED, nothing launched) outside that domain and for
 // shapes beyond their 32-bit offsets; p.out_bs and p.slope are honoured like in corr_forward_direct
-bool corr_dense_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
+CorrPredicate corr_dense_applicable;
 bool corr_dense_forward_pays(const CorrP &p);   // enough workgroups for the dense forward to beat the general kernel (AUTO asks; the debug variant does not)
-int corr_forward_dense(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s);
-int corr_backward_dense(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype,
-                        const CorrP &p, hipStream_t s);
-bool corr_mfma_f32_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_mfma_f32(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H,
-                          int W, int md, int tune, hipStream_t s);
+CorrLauncher corr_forward_dense, corr_backward_dense;
 
-bool corr_f16x2_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_f16x2(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H, int W,
-                       int variant, hipStream_t s);
-int corr_forward_f16x2_wide(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H, int W,
-                            hipStream_t s);   // W > 64 (correlation_f16x2_wide.hip)
+// float tensors on the fp32 matrix cores (correlation_mfma.hip, correlation_mfma_bwd.hip); c.tune: see the launchers
+CorrPredicate corr_mfma_f32_applicable, corr_bwd_mfma_f32_applicable;
+CorrLauncher corr_forward_mfma_f32, corr_backward_mfma_f32;
 
-// half and bfloat16 tensors (dtype FN2_F16 / FN2_BF16; correlation_f16_fwd.hip): one 16-bit MFMA per block product, no split
-bool corr_f16_fwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_f16(int dtype, const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W,
-                     hipStream_t s);
+// float tensors, two-term f16 split (correlation_f16x2*.hip); c.tune: the profiling variant.  _wide: W > 64, called by the other two
+CorrPredicate corr_f16x2_applicable, corr_bwd_f16x2_applicable;
+CorrLauncher corr_forward_f16x2, corr_forward_f16x2_wide, corr_backward_f16x2, corr_backward_f16x2_wide;
+void corr_f16x2_set_debug_buffer(void *p);
+void *corr_f16x2_get_debug_buffer();
 
-// half and bfloat16 tensors, backward (correlation_f16_bwd.hip): one 16-bit MFMA per product, fp32 sums
-bool corr_f16_bwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_backward_f16(int dtype, const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W,
-                      hipStream_t s);
+// half and bfloat16 tensors (correlation_f16_fwd.hip, correlation_f16_bwd.hip): one 16-bit MFMA per block product, no split, fp32 sums
+CorrPredicate corr_f16_fwd_applicable, corr_f16_bwd_applicable;
+CorrLauncher corr_forward_f16, corr_backward_f16;
+
+// double tensors on the fp64 matrix cores (correlation_mfma_f64.hip): FlowNetC's configuration, md = 20
+CorrPredicate corr_mfma_f64_applicable;
+CorrLauncher corr_forward_mfma_f64, corr_backward_mfma_f64;
 
 // Neighbour row blocks of a backward task (FlowNetC's configuration: 4 centre lattice rows per row group rg, displacement radius dr
 // lattice rows, nu = ceil((2 dr + 4) / 4) blocks of 4 neighbour rows: block u holds lattice rows 4rg - dr + 4u .. +3 of a parity
@@ -58,22 +66,5 @@ __host__ __device__ constexpr URange bwd_u_range(int rg, int HL, int dr = 10, in
 }
 static_assert(bwd_u_range(0, 24).lo == 2 && bwd_u_range(1, 24).lo == 1 && bwd_u_range(2, 24).lo == 0 && bwd_u_range(3, 24).hi == 5 &&
               bwd_u_range(4, 24).hi == 4 && bwd_u_range(5, 24).hi == 3 && bwd_u_range(0, 1).lo == 2 && bwd_u_range(0, 1).hi == 2, "real row blocks");
-
-void corr_f16x2_set_debug_buffer(void *p);
-void *corr_f16x2_get_debug_buffer();
-bool corr_bwd_f16x2_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_backward_f16x2(const float *in1, const float *in2, const float *gout, float *g1, float *g2, int B, int C, int H, int W,
-                        int variant, hipStream_t s);
-int corr_backward_f16x2_wide(const float *in1, const float *in2, const float *gout, float *g1, float *g2, int B, int C, int H, int W,
-                             hipStream_t s);   // W > 64 (correlation_f16x2_bwd_wide.hip)
-
-bool corr_bwd_mfma_f32_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_backward_mfma_f32(const float *in1, const float *in2, const float *gout, float *g1, float *g2,
-                           int B, int C, int H, int W, int md, int tune, hipStream_t s);
-
-// double tensors on the fp64 matrix cores (correlation_mfma_f64.hip): FlowNetC's configuration, md = 20
-bool corr_mfma_f64_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2);
-int corr_forward_mfma_f64(const double *in1, const double *in2, double *out, long out_bs, double slope, int B, int C, int H, int W, hipStream_t s);
-int corr_backward_mfma_f64(const double *in1, const double *in2, const double *gout, double *g1, double *g2, int B, int C, int H, int W, hipStream_t s);
 
 } // namespace fn2

@@ -235,11 +235,10 @@ int bwd_dense_md(const void *in1, const void *in2, const void *gout, void *g1, v
 
 } // namespace
 
-bool corr_dense_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_dense_applicable(int dtype, const CorrP &p)
 {
-    (void)H; (void)W;
-    return (dtype == FN2_F32 || dtype == FN2_F16 || dtype == FN2_BF16) && C >= 1 && k == 1 && s1 == 1 && s2 == 1 && pad == md &&
-           md >= 1 && md <= DENSE_MAX_MD;
+    return (dtype == FN2_F32 || dtype == FN2_F16 || dtype == FN2_BF16) && p.C >= 1 && p.k == 1 && p.s1 == 1 && p.s2 == 1 && p.pad == p.md &&
+           p.md >= 1 && p.md <= DENSE_MAX_MD;
 }
 
 // What FN2_CORR_AUTO asks before it takes the dense FORWARD: at least 192 workgroups (batch x 32 x 4-pixel tiles).  A workgroup
@@ -255,27 +254,26 @@ bool corr_dense_forward_pays(const CorrP &p)
     return tiles * p.B >= 192;
 }
 
-int corr_forward_dense(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s)
+int corr_forward_dense(const CorrCall &c, hipStream_t s)
 {
-    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !tiled_fits(p)) return FN2_EUNSUPPORTED;
-    if (p.B == 0) return FN2_OK;
-    switch (dtype) {
-    case FN2_F32: return fwd_dense_md<float>(in1, in2, out, p, s);
-    case FN2_F16: return fwd_dense_md<half_t>(in1, in2, out, p, s);
-    case FN2_BF16: return fwd_dense_md<bf16_t>(in1, in2, out, p, s);
+    if (!corr_dense_applicable(c.dtype, c.p) || !tiled_fits(c.p)) return FN2_EUNSUPPORTED;
+    if (c.p.B == 0) return FN2_OK;
+    switch (c.dtype) {
+    case FN2_F32: return fwd_dense_md<float>(c.in1, c.in2, c.out, c.p, s);
+    case FN2_F16: return fwd_dense_md<half_t>(c.in1, c.in2, c.out, c.p, s);
+    case FN2_BF16: return fwd_dense_md<bf16_t>(c.in1, c.in2, c.out, c.p, s);
     default: return FN2_EUNSUPPORTED;
     }
 }
 
-int corr_backward_dense(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype, const CorrP &p,
-                        hipStream_t s)
+int corr_backward_dense(const CorrCall &c, hipStream_t s)
 {
-    if (!corr_dense_applicable(dtype, p.C, p.H, p.W, p.pad, p.k, p.md, p.s1, p.s2) || !tiled_fits(p)) return FN2_EUNSUPPORTED;
-    if (p.B == 0) return FN2_OK;
-    switch (dtype) {
-    case FN2_F32: return bwd_dense_md<float>(in1, in2, gout, g1, g2, p, s);
-    case FN2_F16: return bwd_dense_md<half_t>(in1, in2, gout, g1, g2, p, s);
-    case FN2_BF16: return bwd_dense_md<bf16_t>(in1, in2, gout, g1, g2, p, s);
+    if (!corr_dense_applicable(c.dtype, c.p) || !tiled_fits(c.p)) return FN2_EUNSUPPORTED;
+    if (c.p.B == 0) return FN2_OK;
+    switch (c.dtype) {
+    case FN2_F32: return bwd_dense_md<float>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
+    case FN2_F16: return bwd_dense_md<half_t>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
+    case FN2_BF16: return bwd_dense_md<bf16_t>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
     default: return FN2_EUNSUPPORTED;
     }
 }

@@ -165,25 +165,24 @@ static int bwd_direct_launch(const void *in1, const void *in2, const void *gout,
     return launch_status();
 }
 
-int corr_forward_direct(const void *in1, const void *in2, void *out, int dtype, const CorrP &p, hipStream_t s)
+int corr_forward_direct(const CorrCall &c, hipStream_t s)
 {
-    switch (dtype) {
-    case FN2_F32: return fwd_direct_launch<float>(in1, in2, out, p, s);
-    case FN2_F16: return fwd_direct_launch<half_t>(in1, in2, out, p, s);
-    case FN2_F64: return fwd_direct_launch<double>(in1, in2, out, p, s);
-    case FN2_BF16: return fwd_direct_launch<bf16_t>(in1, in2, out, p, s);
+    switch (c.dtype) {
+    case FN2_F32: return fwd_direct_launch<float>(c.in1, c.in2, c.out, c.p, s);
+    case FN2_F16: return fwd_direct_launch<half_t>(c.in1, c.in2, c.out, c.p, s);
+    case FN2_F64: return fwd_direct_launch<double>(c.in1, c.in2, c.out, c.p, s);
+    case FN2_BF16: return fwd_direct_launch<bf16_t>(c.in1, c.in2, c.out, c.p, s);
     default: return FN2_EDTYPE;
     }
 }
 
-int corr_backward_direct(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int dtype,
-                         const CorrP &p, hipStream_t s)
+int corr_backward_direct(const CorrCall &c, hipStream_t s)
 {
-    switch (dtype) {
-    case FN2_F32: return bwd_direct_launch<float>(in1, in2, gout, g1, g2, p, s);
-    case FN2_F16: return bwd_direct_launch<half_t>(in1, in2, gout, g1, g2, p, s);
-    case FN2_F64: return bwd_direct_launch<double>(in1, in2, gout, g1, g2, p, s);
-    case FN2_BF16: return bwd_direct_launch<bf16_t>(in1, in2, gout, g1, g2, p, s);
+    switch (c.dtype) {
+    case FN2_F32: return bwd_direct_launch<float>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
+    case FN2_F16: return bwd_direct_launch<half_t>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
+    case FN2_F64: return bwd_direct_launch<double>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
+    case FN2_BF16: return bwd_direct_launch<bf16_t>(c.in1, c.in2, c.gout, c.g1, c.g2, c.p, s);
     default: return FN2_EDTYPE;
     }
 }

@@ -528,24 +528,25 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16(Args<E> p)
 
 } // namespace hbh
 
-bool corr_f16_bwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_f16_bwd_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F16 && dtype != FN2_BF16) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md != 2 * hbh::DR) return false;
-    if (C % hbh::CG != 0 || C < hbh::CG || (H & 1) || (W % 8) != 0 || W > 64) return false;
-    if ((long)C * H * W * 2 >= 0x7fffffffL || (long)hbh::D * hbh::D * H * W * 2 >= 0x7fffffffL) return false;   // 32-bit byte offsets
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md || p.md != 2 * hbh::DR) return false;
+    if (p.C % hbh::CG != 0 || p.C < hbh::CG || (p.H & 1) || (p.W % 8) != 0 || p.W > 64) return false;
+    if ((long)p.C * p.H * p.W * 2 >= 0x7fffffffL || (long)hbh::D * hbh::D * p.H * p.W * 2 >= 0x7fffffffL) return false;   // 32-bit byte offsets
     return true;
 }
 
 // in1, in2, gout, g1, g2: tensors of element type E (half or bfloat16)
 template <class E>
-static int corr_backward_16(const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W, hipStream_t s)
+static int corr_backward_16(const CorrCall &c, hipStream_t s)
 {
-    if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(gout, 16) || !aligned(g1, 16) || !aligned(g2, 16)) return FN2_EALIGN;
+    const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
+    if (!aligned(c.in1, 16) || !aligned(c.in2, 16) || !aligned(c.gout, 16) || !aligned(c.g1, 16) || !aligned(c.g2, 16)) return FN2_EALIGN;
     hbh::Args<E> a;
-    a.nbr[0] = static_cast<const E *>(in2); a.nbr[1] = static_cast<const E *>(in1);
-    a.gout = static_cast<const E *>(gout);
-    a.gin[0] = static_cast<E *>(g1); a.gin[1] = static_cast<E *>(g2);
+    a.nbr[0] = static_cast<const E *>(c.in2); a.nbr[1] = static_cast<const E *>(c.in1);
+    a.gout = static_cast<const E *>(c.gout);
+    a.gin[0] = static_cast<E *>(c.g1); a.gin[1] = static_cast<E *>(c.g2);
     a.B = B; a.C = C; a.H = H; a.W = W;
     a.NRG = (H / 2 + 3) / 4; a.NCGR = C / hbh::CG;
     a.fC = (float)C; a.rC = 1.0f / (float)C;
@@ -557,11 +558,10 @@ static int corr_backward_16(const void *in1, const void *in2, const void *gout, 
     return launch_status();
 }
 
-int corr_backward_f16(int dtype, const void *in1, const void *in2, const void *gout, void *g1, void *g2, int B, int C, int H, int W,
-                      hipStream_t s)
+int corr_backward_f16(const CorrCall &c, hipStream_t s)
 {
-    if (dtype == FN2_BF16) return corr_backward_16<bf16_t>(in1, in2, gout, g1, g2, B, C, H, W, s);
-    return corr_backward_16<half_t>(in1, in2, gout, g1, g2, B, C, H, W, s);
+    if (c.dtype == FN2_BF16) return corr_backward_16<bf16_t>(c, s);
+    return corr_backward_16<half_t>(c, s);
 }
 
 } // namespace fn2

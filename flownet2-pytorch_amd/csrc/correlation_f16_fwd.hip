@@ -527,24 +527,25 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16_wide(ArgsHW<E> p)
 
 } // namespace hh
 
-bool corr_f16_fwd_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_f16_fwd_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F16 && dtype != FN2_BF16) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md / 2 != hf::DR || (md & 1)) return false;
-    if (C % (2 * hh::CKH) != 0 || (H & 1) || (W % 8) != 0) return false;
-    if ((long)C * H * W * 2 >= 0x7fffffffL) return false;   // 32-bit buffer offsets per batch item
-    if ((long)hf::D * hf::D * H * W * 2 >= 0x7fffffffL) return false;   // ... of the output (cf. corr_f16x2_applicable)
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md || p.md / 2 != hf::DR || (p.md & 1)) return false;
+    if (p.C % (2 * hh::CKH) != 0 || (p.H & 1) || (p.W % 8) != 0) return false;
+    if ((long)p.C * p.H * p.W * 2 >= 0x7fffffffL) return false;   // 32-bit buffer offsets per batch item
+    if ((long)hf::D * hf::D * p.H * p.W * 2 >= 0x7fffffffL) return false;   // ... of the output (cf. corr_f16x2_applicable)
     return true;
 }
 
 // in1, in2, out: tensors of element type E (half or bfloat16); out_bs in elements
 template <class E>
-static int corr_forward_16(const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W, hipStream_t s)
+static int corr_forward_16(const CorrCall &c, hipStream_t s)
 {
-    if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(out, 16) || (out_bs % 4) != 0) return FN2_EALIGN;
+    const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
+    if (!aligned(c.in1, 16) || !aligned(c.in2, 16) || !aligned(c.out, 16) || (c.p.out_bs % 4) != 0) return FN2_EALIGN;
     hh::ArgsHW<E> a;
-    a.in1 = static_cast<const E *>(in1); a.in2 = static_cast<const E *>(in2); a.out = static_cast<E *>(out);
-    a.out_bs = out_bs; a.slope = slope;
+    a.in1 = static_cast<const E *>(c.in1); a.in2 = static_cast<const E *>(c.in2); a.out = static_cast<E *>(c.out);
+    a.out_bs = c.p.out_bs; a.slope = c.p.slope;
     a.fC = (float)C; a.rC = 1.0f / (float)C;
     a.B = B; a.C = C; a.H = H; a.W = W;
     a.dbg = nullptr;
@@ -562,11 +563,10 @@ static int corr_forward_16(const void *in1, const void *in2, void *out, long out
     return launch_status();
 }
 
-int corr_forward_f16(int dtype, const void *in1, const void *in2, void *out, long out_bs, float slope, int B, int C, int H, int W,
-                     hipStream_t s)
+int corr_forward_f16(const CorrCall &c, hipStream_t s)
 {
-    if (dtype == FN2_BF16) return corr_forward_16<bf16_t>(in1, in2, out, out_bs, slope, B, C, H, W, s);
-    return corr_forward_16<half_t>(in1, in2, out, out_bs, slope, B, C, H, W, s);
+    if (c.dtype == FN2_BF16) return corr_forward_16<bf16_t>(c, s);
+    return corr_forward_16<half_t>(c, s);
 }
 
 } // namespace fn2

@@ -516,24 +516,25 @@ void corr_f16x2_set_debug_buffer(void *p) { g_debug_buffer = static_cast<unsigne
 void *corr_f16x2_get_debug_buffer() { return g_debug_buffer; }
 #endif
 
-bool corr_f16x2_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_f16x2_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F32) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md / 2 != hf::DR || (md & 1)) return false;
-    if (C % (2 * hf::CK) != 0 || C < 2 * hf::CK || (H & 1) || (W % 8) != 0) return false;   // W > 64: correlation_f16x2_wide.hip
-    if ((long)C * H * W * 4 >= 0x7fffffffL) return false;   // 32-bit buffer offsets per batch item
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md || p.md / 2 != hf::DR || (p.md & 1)) return false;
+    if (p.C % (2 * hf::CK) != 0 || p.C < 2 * hf::CK || (p.H & 1) || (p.W % 8) != 0) return false;   // W > 64: correlation_f16x2_wide.hip
+    if ((long)p.C * p.H * p.W * 4 >= 0x7fffffffL) return false;   // 32-bit buffer offsets per batch item
     // ... of the output too: the epilogue forms (tj * D * H + y) * W * 4 and D * D * H * W * 4 in 32 bits (maps wider than 64 px
     // made this reachable: the task-table limit alone allows H * W up to ~1.6 M).  AUTO then goes on to the general kernel.
-    if ((long)hf::D * hf::D * H * W * 4 >= 0x7fffffffL) return false;
+    if ((long)hf::D * hf::D * p.H * p.W * 4 >= 0x7fffffffL) return false;
     return true;
 }
 
 // variant: 0 = the kernel; other values = profiling switches (fn2_debug.h), only reachable through fn2_debug_*
-int corr_forward_f16x2(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H, int W,
-                       int variant, hipStream_t s)
+int corr_forward_f16x2(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2); float *out = static_cast<float *>(c.out);
+    const long out_bs = c.p.out_bs; const float slope = c.p.slope; const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W, variant = c.tune;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(out, 16) || (out_bs % 4) != 0) return FN2_EALIGN;
-    if (W > 64) return variant == 0 ? corr_forward_f16x2_wide(in1, in2, out, out_bs, slope, B, C, H, W, s) : FN2_EINVAL;
+    if (W > 64) return variant == 0 ? corr_forward_f16x2_wide(c, s) : FN2_EINVAL;
     hf::Args a;
     a.in1 = in1; a.in2 = in2; a.out = out; a.out_bs = out_bs; a.slope = slope;
     a.fC = (float)C; a.rC = 1.0f / (float)C;

@@ -797,21 +797,22 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2(Args p)
 
 } // namespace hb
 
-bool corr_bwd_f16x2_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_bwd_f16x2_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F32) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md || md != 2 * hb::DR) return false;
-    if (C % hb::CG != 0 || C < hb::CG || (H & 1) || (W % 8) != 0) return false;   // W > 64: correlation_f16x2_bwd_wide.hip
-    if ((long)C * H * W * 4 >= 0x7fffffffL || (long)hb::D * hb::D * H * W * 4 >= 0x7fffffffL) return false;
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md || p.md != 2 * hb::DR) return false;
+    if (p.C % hb::CG != 0 || p.C < hb::CG || (p.H & 1) || (p.W % 8) != 0) return false;   // W > 64: correlation_f16x2_bwd_wide.hip
+    if ((long)p.C * p.H * p.W * 4 >= 0x7fffffffL || (long)hb::D * hb::D * p.H * p.W * 4 >= 0x7fffffffL) return false;
     return true;
 }
 
 // which: 0 = both gradients, 1 = gradInput1 only, 2 = gradInput2 only; variant: profiling switches (fn2_debug.h)
-int corr_backward_f16x2(const float *in1, const float *in2, const float *gout, float *g1, float *g2, int B, int C, int H, int W,
-                        int variant, hipStream_t s)
+int corr_backward_f16x2(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2), *gout = static_cast<const float *>(c.gout);
+    float *g1 = static_cast<float *>(c.g1), *g2 = static_cast<float *>(c.g2); const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W, variant = c.tune;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(gout, 16) || !aligned(g1, 16) || !aligned(g2, 16)) return FN2_EALIGN;
-    if (W > 64) return variant == 0 ? corr_backward_f16x2_wide(in1, in2, gout, g1, g2, B, C, H, W, s) : FN2_EINVAL;
+    if (W > 64) return variant == 0 ? corr_backward_f16x2_wide(c, s) : FN2_EINVAL;
     hb::Args a;
     a.nbr[0] = in2; a.nbr[1] = in1; a.gout = gout; a.gin[0] = g1; a.gin[1] = g2;
     a.B = B; a.C = C; a.H = H; a.W = W;

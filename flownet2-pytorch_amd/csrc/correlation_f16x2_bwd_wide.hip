@@ -592,9 +592,10 @@ __global__ __launch_bounds__(NWAVES * 64, 3) void corr_bwd_f16x2_wide(Args p)
 } // namespace hbw
 
 // maps wider than 64 pixels (called by corr_backward_f16x2; same preconditions otherwise)
-int corr_backward_f16x2_wide(const float *in1, const float *in2, const float *gout, float *g1, float *g2, int B, int C, int H, int W,
-                             hipStream_t s)
+int corr_backward_f16x2_wide(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2), *gout = static_cast<const float *>(c.gout);
+    float *g1 = static_cast<float *>(c.g1), *g2 = static_cast<float *>(c.g2); const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(gout, 16) || !aligned(g1, 16) || !aligned(g2, 16)) return FN2_EALIGN;
     hbw::Args a;
     a.nbr[0] = in2; a.nbr[1] = in1; a.gout = gout; a.gin[0] = g1; a.gin[1] = g2;

@@ -466,9 +466,10 @@ __global__ __launch_bounds__(1024, 4) void corr_fwd_f16x2_wide(ArgsW p)
 } // namespace hw
 
 // maps wider than 64 pixels (called by corr_forward_f16x2; same preconditions otherwise)
-int corr_forward_f16x2_wide(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H, int W,
-                            hipStream_t s)
+int corr_forward_f16x2_wide(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2); float *out = static_cast<float *>(c.out);
+    const long out_bs = c.p.out_bs; const float slope = c.p.slope; const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(out, 16) || (out_bs % 4) != 0) return FN2_EALIGN;
     hw::ArgsW a;
     a.in1 = in1; a.in2 = in2; a.out = out; a.out_bs = out_bs; a.slope = slope;

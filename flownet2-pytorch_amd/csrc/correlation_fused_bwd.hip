@@ -69,12 +69,11 @@ extern "C" int fn2_correlation_backward_fused(const void *in1, const void *in2, 
     using namespace fn2;
     const size_t es = dtype_size(dtype);
     if (!es) return FN2_EDTYPE;
-    int nOut = 0, oH = 0, oW = 0;
-    int rc = fn2_correlation_output_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &nOut, &oH, &oW);
+    CorrCall c = {dtype, {}, in1, in2, grad_cat, nullptr, grad_in1, grad_in2, 0};
+    int rc = corr_make_params(c.p, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
     if (rc != FN2_OK) return rc;
-    if (B < 0 || C < 1) return FN2_EINVAL;
     if (stride1 != 1) return FN2_EUNSUPPORTED;                  // as fn2_correlation_backward
-    const long n_item = (long)nOut * oH * oW;
+    const long n_item = c.p.out_bs;
     // the derivative is read off the sign of the stored output: only an increasing activation (slope > 0) keeps that sign
     if (!(negative_slope > 0.0f) || out_batch_stride < n_item || grad_batch_stride < n_item) return FN2_EINVAL;
     if (B == 0) return FN2_OK;
@@ -84,8 +83,7 @@ extern "C" int fn2_correlation_backward_fused(const void *in1, const void *in2, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long total = (long)B * n_item;
     if (negative_slope == 1.0f && grad_batch_stride == n_item)   // identity activation on a contiguous gradient: nothing to do
-        return fn2_correlation_backward_ex(in1, in2, grad_cat, grad_in1, grad_in2, dtype, B, C, H, W, pad_size, kernel_size,
-                                           max_displacement, stride1, stride2, algo, stream);
+        return corr_dispatch(1, c, algo, false, s);
     if (dtype == FN2_F32 && n_item % 4 == 0 && out_batch_stride % 4 == 0 && grad_batch_stride % 4 == 0 && aligned(out_act, 16) &&
         aligned(grad_cat, 16) && aligned(workspace, 16)) {
         long blocks = (total / 4 + 255) / 256;
@@ -108,6 +106,6 @@ extern "C" int fn2_correlation_backward_fused(const void *in1, const void *in2, 
     }
     rc = launch_status();
     if (rc != FN2_OK) return rc;
-    return fn2_correlation_backward_ex(in1, in2, workspace, grad_in1, grad_in2, dtype, B, C, H, W, pad_size, kernel_size,
-                                       max_displacement, stride1, stride2, algo, stream);
+    c.gout = workspace;   // the masked gradient; the inputs' and the gradients' alignment and algo are corr_dispatch's checks
+    return corr_dispatch(1, c, algo, false, s);
 }

@@ -809,12 +809,12 @@ __global__ __launch_bounds__(64 * (16 / NAB), (NST == 1 ? (NAB == 2 ? 4 : 2) : (
 } // namespace mf
 
 // Preconditions of the MFMA forward path.
-bool corr_mfma_f32_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_mfma_f32_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F32) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md) return false;
-    if (md / 2 > mf::DR_MAX || md < 2) return false;
-    if (C % 16 != 0 || (H & 1) || (W & 1)) return false;
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md) return false;
+    if (p.md / 2 > mf::DR_MAX || p.md < 2) return false;
+    if (p.C % 16 != 0 || (p.H & 1) || (p.W & 1)) return false;
     return true;
 }
 
@@ -849,9 +849,10 @@ static int launch_nv(const Args &a, long ntasks, hipStream_t s)
 
 // tune: 0 = fastest applicable kernel (bf16x3 split where it applies, else fp32 MFMA); 2 = fp32 MFMA only
 //       (v_mfma_f32_16x16x4_f32, bitwise an fmaf chain); 3 = bf16x3 only; >= 100 profiling instantiations
-int corr_forward_mfma_f32(const float *in1, const float *in2, float *out, long out_bs, float slope, int B, int C, int H,
-                          int W, int md, int tune, hipStream_t s)
+int corr_forward_mfma_f32(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2); float *out = static_cast<float *>(c.out);
+    const long out_bs = c.p.out_bs; const float slope = c.p.slope; const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W, md = c.p.md; int tune = c.tune;
     if (!aligned(in1, 8) || !aligned(in2, 8)) return FN2_EALIGN;
     if (out_bs % 2 != 0) return FN2_EALIGN;   // output rows are stored as float2
     mf::Args a;

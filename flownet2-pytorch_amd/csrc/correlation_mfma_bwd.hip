@@ -645,10 +645,10 @@ static int launch_nv(int NV, const Args &a, long ntasks, hipStream_t s)
 
 } // namespace mb
 
-bool corr_bwd_mfma_f32_applicable(int dtype, int C, int H, int W, int pad, int k, int md, int s1, int s2)
+bool corr_bwd_mfma_f32_applicable(int dtype, const CorrP &p)
 {
-    if (!corr_mfma_f32_applicable(dtype, C, H, W, pad, k, md, s1, s2)) return false;
-    return C % 32 == 0;
+    if (!corr_mfma_f32_applicable(dtype, p)) return false;
+    return p.C % 32 == 0;
 }
 
 // bf16x3 kernel preconditions beyond corr_bwd_mfma_f32_applicable: radius 10 (FlowNetC: max_displacement 20 or 21), C % 64,
@@ -663,9 +663,10 @@ static bool bwd_bf16x3_ok(const float *in1, const float *in2, const float *gout,
 //       6 = fp32 MFMA kernel, both gradients in one launch, 64- or 32-channel groups (see below); 1 = force 32-channel
 //           groups; 2 = force 64; 3 = one launch per gradient; 10 + v = its profiling variant v;
 //       4 = bf16x3 kernel or FN2_EUNSUPPORTED; 5 = bf16x3 with 64-px tiles; 40 + v = its profiling variant v
-int corr_backward_mfma_f32(const float *in1, const float *in2, const float *gout, float *g1, float *g2,
-                           int B, int C, int H, int W, int md, int tune, hipStream_t s)
+int corr_backward_mfma_f32(const CorrCall &c, hipStream_t s)
 {
+    const float *in1 = static_cast<const float *>(c.in1), *in2 = static_cast<const float *>(c.in2), *gout = static_cast<const float *>(c.gout);
+    float *g1 = static_cast<float *>(c.g1), *g2 = static_cast<float *>(c.g2); const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W, md = c.p.md; int tune = c.tune;
     if (!aligned(in1, 8) || !aligned(in2, 8) || !aligned(gout, 8)) return FN2_EALIGN;
     if ((long)(2 * (md / 2) + 1) * (2 * (md / 2) + 1) * H * W >= (1L << 31)) return FN2_EUNSUPPORTED;
     mb::Args a;

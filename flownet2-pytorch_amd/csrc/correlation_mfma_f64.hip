@@ -385,17 +385,19 @@ __global__ __launch_bounds__(512, 1) void corr_bwd_mfma_f64(BArgs p)
 
 } // namespace md
 
-bool corr_mfma_f64_applicable(int dtype, int C, int H, int W, int pad, int k, int md_, int s1, int s2)
+bool corr_mfma_f64_applicable(int dtype, const CorrP &p)
 {
     if (dtype != FN2_F64) return false;
-    if (k != 1 || s1 != 1 || s2 != 2 || pad != md_ || md_ != 2 * md::DR) return false;
-    if (C % md::BCG != 0 || (H & 1) || (W & 1)) return false;
-    if ((long)md::D * md::D * H * W >= 0x7fffffffL / 8) return false;
+    if (p.k != 1 || p.s1 != 1 || p.s2 != 2 || p.pad != p.md || p.md != 2 * md::DR) return false;
+    if (p.C % md::BCG != 0 || (p.H & 1) || (p.W & 1)) return false;
+    if ((long)md::D * md::D * p.H * p.W >= 0x7fffffffL / 8) return false;
     return true;
 }
 
-int corr_forward_mfma_f64(const double *in1, const double *in2, double *out, long out_bs, double slope, int B, int C, int H, int W, hipStream_t s)
+int corr_forward_mfma_f64(const CorrCall &c, hipStream_t s)
 {
+    const double *in1 = static_cast<const double *>(c.in1), *in2 = static_cast<const double *>(c.in2); double *out = static_cast<double *>(c.out);
+    const long out_bs = c.p.out_bs; const double slope = (double)c.p.slope; const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(out, 16) || (out_bs % 2) != 0) return FN2_EALIGN;
     md::FArgs a;
     a.in1 = in1; a.in2 = in2; a.out = out; a.out_bs = out_bs; a.slope = slope;
@@ -408,8 +410,10 @@ int corr_forward_mfma_f64(const double *in1, const double *in2, double *out, lon
     return launch_status();
 }
 
-int corr_backward_mfma_f64(const double *in1, const double *in2, const double *gout, double *g1, double *g2, int B, int C, int H, int W, hipStream_t s)
+int corr_backward_mfma_f64(const CorrCall &c, hipStream_t s)
 {
+    const double *in1 = static_cast<const double *>(c.in1), *in2 = static_cast<const double *>(c.in2), *gout = static_cast<const double *>(c.gout);
+    double *g1 = static_cast<double *>(c.g1), *g2 = static_cast<double *>(c.g2); const int B = c.p.B, C = c.p.C, H = c.p.H, W = c.p.W;
     if (!aligned(in1, 16) || !aligned(in2, 16) || !aligned(gout, 16) || !aligned(g1, 8) || !aligned(g2, 8)) return FN2_EALIGN;
     md::BArgs a;
     a.nbr[0] = in2; a.nbr[1] = in1; a.gout = gout; a.gin[0] = g1; a.gin[1] = g2;

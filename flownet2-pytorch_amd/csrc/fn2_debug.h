@@ -17,6 +17,12 @@
 
 #define FN2_DEBUG_CORR_DENSE 9000
 
+/* rows of the correlation dispatcher's kernel table (capi.hip), in the order FN2_CORR_AUTO tries them: half / bfloat16 tensors
+ * (correlation_f16_*.hip), float with the f16 split (correlation_f16x2*.hip), float on the fp32 / bf16x3 matrix kernels
+ * (correlation_mfma*.hip), double (correlation_mfma_f64.hip), dense stride-1 volumes (correlation_dense.hip), the general kernel */
+enum { FN2_CORR_KERNEL_H16, FN2_CORR_KERNEL_F16X2, FN2_CORR_KERNEL_MFMA_F32, FN2_CORR_KERNEL_F64, FN2_CORR_KERNEL_DENSE,
+       FN2_CORR_KERNEL_DIRECT, FN2_CORR_KERNEL_COUNT };
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -27,6 +33,14 @@ int fn2_debug_correlation_forward(const void *in1, const void *in2, void *out, i
 int fn2_debug_correlation_backward(const void *in1, const void *in2, const void *grad_out, void *grad_in1, void *grad_in2,
                                    int dtype, int B, int C, int H, int W, int pad_size, int kernel_size,
                                    int max_displacement, int stride1, int stride2, int variant, void *stream);
+/* What would this call run?  Nothing is launched and no pointer dereferenced (a host test may pass 0x1000).  direction 0:
+ * fn2_correlation_forward_fused(in1, in2, out, out_batch_stride, slope 1, ..., algo), with out_batch_stride 0 fn2_correlation_forward_ex;
+ * direction 1: fn2_correlation_backward_ex(in1, in2, grad_out = out, grad_in1, grad_in2, ..., algo); algo >= 100: that variant of the two
+ * entry points above.  Returns how many FN2_CORR_KERNEL_* the dispatcher would try, the first max_ids of them in ids[] in its order (a
+ * launcher that declines hands over to the next), or the negative code the entry point returns before any launch. */
+int fn2_debug_correlation_plan(int direction, const void *in1, const void *in2, void *out, void *grad_in1, void *grad_in2,
+                               int64_t out_batch_stride, int dtype, int B, int C, int H, int W, int pad_size, int kernel_size,
+                               int max_displacement, int stride1, int stride2, int algo, int *ids, int max_ids);
 /* resample2d with profiling switches in `flags` (bit 8: untiled kernels, bits 9-11: backward ablations, bits 12-13: tile
  * height 1 = 48, 2 = 32, 3 = 64 rows); the public entry points only look at bilinear != 0 */
 int fn2_debug_resample2d_forward(const float *img, const int64_t *img_strides, const float *flow, float *out,

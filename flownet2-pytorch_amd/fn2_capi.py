@@ -32,7 +32,8 @@ EXPORTS = [
 # libflownet2_hip_debug.so only
 DEBUG_EXPORTS = ["fn2_debug_correlation_forward", "fn2_debug_correlation_backward", "fn2_debug_set_buffer",
                  "fn2_debug_resample2d_forward", "fn2_debug_resample2d_backward", "fn2_debug_stream_copy", "fn2_debug_mfma_probe",
-                 "fn2_debug_xcc_census"]
+                 "fn2_debug_xcc_census", "fn2_debug_correlation_plan"]
+CORR_KERNELS = ("H16", "F16X2", "MFMA_F32", "F64", "DENSE", "DIRECT")   # csrc/fn2_debug.h FN2_CORR_KERNEL_*, in FN2_CORR_AUTO's order
 
 # the one debug variant whose results are correct: the dense stride-1 kernels (csrc/correlation_dense.hip) by name, for
 # correlation_forward / correlation_backward(..., algo=FN2_DEBUG_CORR_DENSE); FN2_EUNSUPPORTED outside their domain
@@ -192,6 +193,17 @@ def correlation_forward(in1, in2, pad, k, md, s1, s2, algo=FN2_CORR_AUTO, out=No
     with torch.cuda.device_of(in1):
         check(fn(_p(in1), _p(in2), _p(out), _dtype_code(in1), B, C, H, W, pad, k, md, s1, s2, algo, _stream(in1)), what)
     return out
+
+
+def correlation_plan(direction, dtype, shape, pad, k, md, s1, s2, algo=FN2_CORR_AUTO, ptrs=(0x1000,) * 5, out_bs=0):
+    """fn2_debug_correlation_plan (needs no GPU): the CORR_KERNELS the dispatcher would try for this call, in its order, or the negative
+    code the entry point returns before any launch.  ``ptrs``: addresses (never dereferenced) of in1, in2, out ("forward"; ``out_bs``: the
+    output's batch stride, 0 = contiguous) or in1, in2, grad_out, grad_in1, grad_in2 ("backward"); ``algo`` >= 100: a debug variant."""
+    ids = (ctypes.c_int * len(CORR_KERNELS))()
+    ptrs = [ctypes.c_void_p(a) for a in tuple(ptrs) + (0,) * (5 - len(ptrs))]
+    n = debug_lib().fn2_debug_correlation_plan({"forward": 0, "backward": 1}[direction], *ptrs, ctypes.c_int64(out_bs), dtype, *shape,
+                                               pad, k, md, s1, s2, algo, ids, len(ids))
+    return n if n < 0 else [CORR_KERNELS[i] for i in ids[:n]]
 
 
 def correlation1d_output_shape(H, W, pad, md, s1, s2, sd=0):

@@ -95,6 +95,40 @@ def test_rejected_calls_return_codes_without_gpu():
     assert ml(outs, p, p, None, w1, f32(1.0), 3, 1, 8, 8, 4, 1, f32(0.05), p, ctypes.c_size_t(1 << 20), null) == -1    # norm must be 1 or 2
     assert ml(outs, p, p, None, w1, f32(1.0), 2, 1, 8, 8, 3, 1, f32(0.05), p, ctypes.c_size_t(1 << 20), null) == -1    # start_scale not a power of two
     assert ml(outs, p, p, None, w1, f32(1.0), 2, 1, 8, 8, 4, 1, f32(0.05), p, ctypes.c_size_t(0), null) == -1          # workspace too small
+    for what, rc, want in rejected_correlation_calls(lib, fn2_capi.debug_lib()):
+        assert rc == want, what
+
+
+def rejected_correlation_calls(lib, dbg):
+    """(what, code, expected code) of the correlation dispatcher's calls that end before any launch: every case of
+    tests/corr_dispatch_cases.py whose plan is a code, through the entry point the plan speaks of -- fn2_correlation_forward_ex /
+    _backward_ex, fn2_correlation_backward_fused as well (identity activation on a contiguous gradient: no mask pass in front of
+    the dispatcher) and the debug entry points for a variant -- and the one rejection a plan cannot see, a launcher's own alignment
+    check.  The expected codes are those of the if-chains the kernel table replaced.  Addresses are never dereferenced."""
+    import corr_dispatch_cases as cases
+    i64, f32, null = ctypes.c_int64, ctypes.c_float, ctypes.c_void_p(0)
+    for what, direction, dtype, shape, params, kw, want in cases.FORWARD_AUTO + cases.FORWARD_FORCED + cases.BACKWARD_AUTO + cases.DEBUG:
+        if not isinstance(want, int):
+            continue
+        algo = kw.get("algo", fn2_capi.FN2_CORR_AUTO)
+        ptrs = [ctypes.c_void_p(a) for a in kw.get("ptrs", (cases.A16,) * 5)]
+        tail = (dtype,) + shape + params + (algo, null)
+        if direction == "forward":
+            fn = dbg.fn2_debug_correlation_forward if algo >= 100 else lib.fn2_correlation_forward_ex
+            yield what, fn(*ptrs[:3], *tail), want
+        else:
+            fn = dbg.fn2_debug_correlation_backward if algo >= 100 else lib.fn2_correlation_backward_ex
+            yield what, fn(*ptrs, *tail), want
+    a16 = ctypes.c_void_p(cases.A16)
+    yield "bwd stride1 2 (fused)", lib.fn2_correlation_backward_fused(a16, a16, a16, i64(1 << 20), a16, i64(1 << 20), f32(0.1), a16, ctypes.c_size_t(1 << 40),
+                                                                      a16, a16, cases.F32, 1, 4, 8, 8, 4, 1, 4, 2, 2, 0, null), cases.EUNSUPPORTED
+    for algo, want in ((5, cases.EINVAL), (-1, cases.EINVAL), (fn2_capi.FN2_CORR_MFMA_F16X2, cases.EUNSUPPORTED)):   # on (1, 16, 2, 2), md 4
+        tail = (cases.F32,) + cases.SMALL + cases.md(4) + (algo, null)
+        yield "bwd algo %d" % algo, lib.fn2_correlation_backward_ex(a16, a16, a16, a16, a16, *tail), want
+        yield "bwd algo %d (fused)" % algo, lib.fn2_correlation_backward_fused(a16, a16, a16, i64(25 * 2 * 2), a16, i64(25 * 2 * 2), f32(1.0), a16,
+                                                                              ctypes.c_size_t(1 << 40), a16, a16, *tail), want
+    yield "half, forced f16x2, in1 off by 2 bytes", lib.fn2_correlation_forward_ex(
+        ctypes.c_void_p(cases.A16 + 2), a16, a16, cases.HALF, 1, 128, 2, 8, *cases.P20, fn2_capi.FN2_CORR_MFMA_F16X2, null), cases.EALIGN
 
 
 def test_float32_warp_entry_points_check_in_a_fixed_order():
