@@ -23,8 +23,9 @@ static inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<u
 // Zero fill of n 32-bit words at a 4-byte aligned address, as a kernel: words up to the first 16-byte boundary, 16-byte stores, the
 // last words.  The libraries clear what their atomics add into with this, not with hipMemsetAsync.  Observed, not explained: captured
 // into a hipGraph through torch.cuda.graph on this runtime, the hipMemsetAsync of these buffers did not clear them on replay
-// (tests/test_gpu_pipelines.py: the scatters then added onto uninitialised memory or onto the last replay's sums), while the same
-// call outside a graph always did; why the memset node fails has not been found.  A kernel node replays like the kernels around it.
+// (tests/test_gpu_pipelines.py: the scatters then added onto uninitialised memory or onto the last replay's sums; tests/
+// test_gpu_capi_graph.py: the MultiScale ticket counter and the empty batch's sums), while the same call outside a graph always did;
+// why the memset node fails has not been found.  A kernel node replays like the kernels around it.  No library enqueues a memset node.
 template <int = 0> __global__ void __launch_bounds__(256) zero_fill_kernel(unsigned *p, size_t n)
 {
     const size_t to16 = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4;

@@ -287,12 +287,14 @@ static int ms_launch(const float *const *outputs, const float *target, float *su
         a.coef[i] = (weights && px > 0) ? (float)((double)weights[i] / (2.0 * px)) : 0.0f;
         a.coef[num_scales + i] = (weights && px > 0) ? (float)((double)weights[i] / px) : 0.0f;
     }
+    // every clear below is a kernel (zero_fill_async, fn2_common.h), not a memset node: captured into a hipGraph the memset nodes of
+    // these three places did not do their work on replay (tests/test_gpu_capi_graph.py)
     if (nblocks == 0) {   // empty batch: every sum is zero
-        hipError_t e = hipMemsetAsync(sums, 0, 2 * num_scales * sizeof(float), s);
-        if (e == hipSuccess && loss_epe) e = hipMemsetAsync(loss_epe, 0, 2 * sizeof(float), s);
-        return e == hipSuccess ? FN2_OK : (int)e;
+        rc = zero_fill_async(sums, 2 * num_scales * sizeof(float), s);
+        if (rc == FN2_OK && loss_epe) rc = zero_fill_async(loss_epe, 2 * sizeof(float), s);
+        return rc;
     }
-    if (!primed && hipMemsetAsync(a.ticket, 0, sizeof(unsigned), s) != hipSuccess) return launch_status();
+    if (!primed && (rc = zero_fill_async(a.ticket, sizeof(unsigned), s)) != FN2_OK) return rc;
     hipLaunchKernelGGL(multiscale_l1_epe_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, a);
     return launch_status();
 }

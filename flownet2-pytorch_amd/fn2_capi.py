@@ -514,13 +514,14 @@ def forward_warp_forward_det(inp, flow, out=None, workspace=None):
     return out
 
 
-def forward_warp_backward(inp, flow, gout, want_input=True, want_flow=True):
-    """fn2s_forward_warp_backward: (grad_input, grad_flow), None for one that is not wanted (its pointer is passed as NULL)."""
+def forward_warp_backward(inp, flow, gout, want_input=True, want_flow=True, out=(None, None)):
+    """fn2s_forward_warp_backward: (grad_input, grad_flow), None for one that is not wanted (its pointer is passed as NULL); ``out``:
+    preallocated results."""
     import torch
     B, C, H, W = _splat_shape(inp, flow)
     assert gout.is_contiguous() and gout.shape == inp.shape
-    gi = torch.empty_like(inp) if want_input else None
-    gf = torch.empty_like(flow) if want_flow else None
+    gi = (out[0] if out[0] is not None else torch.empty_like(inp)) if want_input else None
+    gf = (out[1] if out[1] is not None else torch.empty_like(flow)) if want_flow else None
     null = ctypes.c_void_p(0)
     with torch.cuda.device_of(inp):
         check(splat_lib().fn2s_forward_warp_backward(_p(inp), _p(flow), _p(gout), _p(gi) if want_input else null, _p(gf) if want_flow else null,

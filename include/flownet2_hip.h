@@ -409,8 +409,8 @@ int fn2_multiscale_loss(const float *const *outputs, const float *target, float 
  * -- by the last workgroup to finish (a ticket counter in the first 64 bytes of `workspace`, the same place for every geometry; the summation order is fixed, the result
  * deterministic), so that loss and metric cost ONE launch.  workspace_primed != 0: the caller guarantees that the workspace was
  * zero-filled once and has since only been used by this entry point on one stream at a time (the kernel leaves the counter at
- * zero) -- for any geometry that fits it, not only the one it was first used with; 0: the counter is cleared by a 4-byte memset
- * node in front of the kernel (any scratch memory will do).  `weights` and `loss_epe` are required: FN2_EINVAL without them. */
+ * zero) -- for any geometry that fits it, not only the one it was first used with; 0: the counter is cleared by a small
+ * kernel in front of the kernel (any scratch memory will do; a kernel, not a memset node, so that it also clears on the replay of a hipGraph).  `weights` and `loss_epe` are required: FN2_EINVAL without them. */
 int fn2_multiscale_loss_fused(const float *const *outputs, const float *target, float *sums, float *loss_epe, float *const *grads,
                               const float *weights, float grad_scale, int norm, int B, int H, int W, int start_scale, int num_scales,
                               float div_flow, void *workspace, size_t workspace_bytes, int workspace_primed, void *stream);

@@ -82,7 +82,7 @@ def test_modules_run_without_the_gil_in_backward(dev):
 
 def test_multiscale_node_one_launch_and_repeatable(dev):
     """N3 through multiscale_loss_cuda: loss and metric come from the kernel's last workgroup (no second launch), the cached
-    workspace's ticket counter is left at zero (call after call gives the same bits), the raw-sums entry point of the C ABI (memset
+    workspace's ticket counter is left at zero (call after call gives the same bits), the raw-sums entry point of the C ABI (a clear
     in front, any scratch) agrees, and the backward scales out of place."""
     import multiscale_loss_cuda
     import fn2_capi
@@ -102,7 +102,7 @@ def test_multiscale_node_one_launch_and_repeatable(dev):
             first = cur
         assert torch.equal(cur[0], first[0]) and torch.equal(cur[1], first[1]) and all(torch.equal(x, y) for x, y in zip(cur[2], first[2])), rep
     assert not epe.requires_grad and loss.requires_grad
-    sums, _ = fn2_capi.multiscale_l1_epe(outs, target, weights)                  # un-primed scratch, memset node in front of the kernel
+    sums, _ = fn2_capi.multiscale_l1_epe(outs, target, weights)                  # un-primed scratch, a clear kernel in front of the kernel
     sums2 = multiscale_loss_cuda.sums(target, outs, 4, 0.05)
     assert torch.equal(sums, sums2)
     n = [o.numel() for o in outs]

@@ -205,7 +205,7 @@ def test_levels_without_elements(dev, norm):
 
 @pytest.mark.parametrize("norm", [1, 2])
 def test_empty_batch(dev, norm):
-    """B = 0: all sums are 0 and nothing is launched (the scratch memory is not touched, not even the ticket counter's memset)."""
+    """B = 0: all sums are 0 and nothing is launched (the scratch memory is not touched, not even the ticket counter's clear)."""
     import multiscale_loss_cuda
     shape = (0, 32, 32, 4, 2)
     w = [0.32, 0.16]
