@@ -17,6 +17,92 @@ import fn2_capi
 import multiscale_loss_cuda  # built by flownet2-pytorch_amd/build.py (csrc/binding/multiscale_loss_cuda.cpp); no fallback on purpose
 
 
+import fn2_ops
+from fn2_ops import refuse
+
+_PREDICTION_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+# ---- the fn2 operators (fn2_ops.py), for torch.compile.  The forward operator IS multiscale_loss_cuda.apply on detached
+# predictions, so the loss and the metric have the eager node's bits by construction (the kernel's last workgroup forms them).  The eager
+# node keeps the unit gradients its forward pass wrote; an operator has nowhere to keep them, so the backward operator runs the pass again
+# through fn2_capi.multiscale_l1_epe -- the same kernel with the same factors -- and scales what it wrote by grad_loss.
+def _multiscale_forward(target, outputs, start_scale, div_flow, weights, norm):
+    with torch.no_grad():
+        loss, epe = multiscale_loss_cuda.apply(target, [o.detach() for o in outputs], start_scale, div_flow, list(weights), norm)
+    return loss.clone(), epe.clone()      # (two views of one tensor: an operator's results must not share memory)
+
+
+def _multiscale_fake_inputs(target, outputs, start_scale, weights, norm, op):
+    n = len(outputs)
+    refuse(1 <= n <= 5 and len(weights) == n, op, ": 1..5 predictions with one weight each expected, got ", n, " / ", len(weights))
+    refuse(target.dim() == 4 and target.shape[1] == 2 and target.dtype == torch.float32, op, ": target must be float32 B x 2 x H x W, got ",
+           tuple(target.shape))
+    refuse(norm in (1, 2), op, ": norm must be 1 (L1) or 2 (L2)")
+    refuse(start_scale >= 1, op, ": unsupported geometry (start_scale ", start_scale, ", ", n, " scales)")
+    B, _, H, W = target.shape
+    for i, o in enumerate(outputs):
+        k = start_scale << i
+        refuse(o.dtype in _PREDICTION_DTYPES, op, ": predictions must be float32, float16 or bfloat16, got ", o.dtype)
+        refuse(o.dim() == 4 and o.shape[0] == B and o.shape[1] == 2 and o.shape[2] == H // k and o.shape[3] == W // k, op, ": prediction ", i,
+               " has shape ", tuple(o.shape), ", expected [", B, ", 2, ", H // k, ", ", W // k, "]")
+
+
+def _multiscale_forward_fake(target, outputs, start_scale, div_flow, weights, norm):
+    _multiscale_fake_inputs(target, outputs, start_scale, weights, norm, "fn2::multiscale_loss")
+    return target.new_empty(()), target.new_empty(())
+
+
+def _multiscale_backward(target, outputs, grad_loss, start_scale, div_flow, weights, norm, need):
+    wide = [o.detach().float().contiguous() for o in outputs]
+    _, unit = fn2_capi.multiscale_l1_epe(wide, target.contiguous(), weights, start_scale, div_flow, want_grads=True, norm=norm)
+    scale = grad_loss.float()
+    return [(g * scale).to(o.dtype) if wanted else o.new_empty(0) for g, o, wanted in zip(unit, outputs, need)]
+
+
+def _multiscale_backward_fake(target, outputs, grad_loss, start_scale, div_flow, weights, norm, need):
+    _multiscale_fake_inputs(target, outputs, start_scale, weights, norm, "fn2::multiscale_loss_backward")
+    refuse(len(need) == len(outputs), "fn2::multiscale_loss_backward: one flag per prediction expected")
+    return [o.new_empty(o.shape) if wanted else o.new_empty(0) for o, wanted in zip(outputs, need)]
+
+
+def _multiscale_setup(ctx, inputs, output):
+    target, outputs = inputs[0], inputs[1]
+    ctx.save_for_backward(target, *outputs)
+    ctx.options = tuple(inputs[2:])
+    ctx.need = tuple(o.requires_grad for o in outputs)      # (needs_input_grad has one flag for the whole list)
+
+
+def _multiscale_grad(ctx, grad_loss, _grad_epe):
+    target, *outputs = ctx.saved_tensors
+    grads = [None] * len(outputs)
+    if any(ctx.need) and grad_loss is not None:
+        got = _multiscale_backward_op(target, outputs, grad_loss, *ctx.options, list(ctx.need))
+        grads = [g if wanted else None for g, wanted in zip(got, ctx.need)]
+    return None, grads, None, None, None, None
+
+
+_multiscale_forward_op = fn2_ops.define(
+    "multiscale_loss", "(Tensor target, Tensor[] outputs, int start_scale, float div_flow, float[] weights, int norm) -> (Tensor, Tensor)",
+    _multiscale_forward, _multiscale_forward_fake, _multiscale_grad, _multiscale_setup)
+_multiscale_backward_op = fn2_ops.define(
+    "multiscale_loss_backward",
+    "(Tensor target, Tensor[] outputs, Tensor grad_loss, int start_scale, float div_flow, float[] weights, int norm, bool[] need) -> Tensor[]",
+    _multiscale_backward, _multiscale_backward_fake)
+
+
+def _traced_apply(target, outputs, start_scale=4, div_flow=0.05, weights=(), norm=1):
+    loss, epe = _multiscale_forward_op(target, list(outputs), start_scale, div_flow, list(weights), norm)
+    return [loss, epe.detach()]
+
+
+# MultiScale.forward is unchanged and pays nothing in eager: Dynamo is told to trace the function above wherever it meets the builtin
+try:
+    torch.compiler.substitute_in_graph(multiscale_loss_cuda.apply, skip_signature_check=True)(_traced_apply)
+except ValueError:      # this module executed a second time (importlib.reload): the builtin already has its stand-in
+    pass
+
+
 def EPE(input_flow, target_flow):
     """losses.py:11-12."""
     return torch.norm(target_flow - input_flow, p=2, dim=1).mean()
@@ -67,7 +153,8 @@ class MultiScale(nn.Module):
             epe = EPE(output, target)
             return [torch.abs(output - target).mean() if self._norm == 1 else torch.norm(output - target, p=2, dim=1).mean(), epe]
         assert isinstance(output, (tuple, list)) and len(output) == self.numScales
-        if target.is_cuda:
+        # (compiling: Dynamo traces the builtin as the fn2 operator, on fake tensors of any device; a GPU call never evaluates the second test)
+        if target.is_cuda or torch.compiler.is_compiling():
             loss, epe = multiscale_loss_cuda.apply(target, list(output), self.startScale, self.div_flow, self.loss_weights, self._norm)
             return [loss, epe]
         key = (target.device, tuple(o.numel() for o in output))

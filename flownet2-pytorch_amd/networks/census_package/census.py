@@ -15,6 +15,59 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import census_cuda  # built by flownet2-pytorch_amd/build.py; no fallback on purpose
+import fn2_ops
+from fn2_ops import refuse
+
+
+# ---- the fn2 operators (fn2_ops.py): the same binding calls as the static methods below, for torch.compile
+def _fake_inputs(im1, im2, max_distance, scale, op):
+    """check_inputs of csrc/binding/census_cuda.cpp, as far as shapes, dtypes and parameters decide it."""
+    refuse(im1.dim() == 4 and im2.dim() == 4, op, ": im1 and im2 must be 4-D (N, C, H, W); add the missing dimensions with [None]")
+    refuse(im1.shape == im2.shape, op, ": im2 ", tuple(im2.shape), " must have the shape of im1 ", tuple(im1.shape))
+    refuse(im1.shape[1] == 1 or im1.shape[1] == 3, op, ": the images have ", im1.shape[1], " channels, expected 1 (grey) or 3 (RGB)")
+    refuse(1 <= max_distance <= census_cuda.MAX_DISTANCE, op, ": max_distance ", max_distance, " is not 1, 2 or 3")
+    refuse(abs(scale) <= 3.4028234663852886e38, op, ": scale ", scale, " is not a finite float")
+    for name, t in (("im1", im1), ("im2", im2)):
+        refuse(t.dtype == torch.float32, op, ": ", name, " must be float32, got ", t.dtype, ": convert it with .float()")
+
+
+def _forward_fake(im1, im2, max_distance, scale, normalize):
+    _fake_inputs(im1, im2, max_distance, scale, "fn2::census")
+    return im1.new_empty((im1.shape[0], 1, im1.shape[2], im1.shape[3]))
+
+
+def _backward(im1, im2, grad_output, max_distance, scale, normalize, want1, want2):
+    grad1, grad2 = census_cuda.backward_alloc(im1, im2, grad_output, max_distance, scale, normalize, want1, want2)
+    return (grad1 if want1 else im1.new_empty(0)), (grad2 if want2 else im1.new_empty(0))
+
+
+def _backward_fake(im1, im2, grad_output, max_distance, scale, normalize, want1, want2):
+    _fake_inputs(im1, im2, max_distance, scale, "fn2::census_backward")
+    refuse(want1 or want2, "fn2::census_backward: neither gradient is wanted")
+    return (im1.new_empty(im1.shape) if want1 else im1.new_empty(0)), (im1.new_empty(im1.shape) if want2 else im1.new_empty(0))
+
+
+def _setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.options = tuple(inputs[2:])
+
+
+def _grad(ctx, grad_output):
+    im1, im2 = ctx.saved_tensors
+    want1, want2 = ctx.needs_input_grad[:2]
+    if not (want1 or want2):
+        return None, None, None, None, None
+    grad1, grad2 = _backward_op(im1, im2, grad_output, *ctx.options, want1, want2)
+    return (grad1 if want1 else None), (grad2 if want2 else None), None, None, None
+
+
+_forward_op = fn2_ops.define("census", "(Tensor im1, Tensor im2, int max_distance, float scale, bool normalize) -> Tensor",
+                             census_cuda.forward_alloc, _forward_fake, _grad, _setup)
+# a gradient that is not wanted comes back with numel 0 (a schema has no optional result) and is not computed
+_backward_op = fn2_ops.define(
+    "census_backward",
+    "(Tensor im1, Tensor im2, Tensor grad_output, int max_distance, float scale, bool normalize, bool want1, bool want2) -> (Tensor, Tensor)",
+    _backward, _backward_fake)
 
 
 class CensusFunction(Function):
@@ -29,6 +82,8 @@ class CensusFunction(Function):
     def forward(ctx, im1, im2, max_distance=3, scale=255.0, normalize=True):
         ctx.save_for_backward(im1, im2)
         ctx.options = (int(max_distance), float(scale), bool(normalize))
+        if torch.compiler.is_compiling():   # Dynamo traces apply() through this method: the operator it can see
+            return _forward_op(im1, im2, *ctx.options)
         return census_cuda.forward_alloc(im1, im2, *ctx.options)
 
     @staticmethod
@@ -38,6 +93,9 @@ class CensusFunction(Function):
         want1, want2 = ctx.needs_input_grad[:2]
         if not (want1 or want2):
             return None, None, None, None, None
+        if torch.compiler.is_compiling():
+            grad1, grad2 = _backward_op(im1, im2, grad_output, *ctx.options, want1, want2)
+            return (grad1 if want1 else None), (grad2 if want2 else None), None, None, None
         return tuple(census_cuda.backward_alloc(im1, im2, grad_output, *ctx.options, want1, want2)) + (None, None, None)
 
 

@@ -17,11 +17,67 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import corr_lookup_cuda  # built by flownet2-pytorch_amd/build.py; no fallback on purpose
+import fn2_ops
+from fn2_ops import refuse
+
+MAX_RADIUS = 8   # FN2L_MAX_RADIUS (include/flownet2_hip_lookup.h)
+
+
+# ---- the fn2 operators (fn2_ops.py): the same binding calls as the static methods below, for torch.compile
+def _fake_inputs(fmap1, fmap2, coords, radius, op):
+    """check_inputs of csrc/binding/corr_lookup_cuda.cpp, as far as shapes and dtypes decide it."""
+    refuse(fmap2.dtype == fmap1.dtype and coords.dtype == fmap1.dtype, op, ": fmap2 and coords must have the dtype of fmap1, ", fmap1.dtype)
+    refuse(fmap1.dtype == torch.float32, op, ": float32 tensors expected, got ", fmap1.dtype,
+           " (RAFT calls its lookup in float under autocast: use .float())")
+    refuse(fmap1.dim() == 4 and fmap2.dim() == 4 and coords.dim() == 4, op, ": fmap1, fmap2 and coords must be 4-D (N, C, H, W)")
+    refuse(fmap2.shape[0] == fmap1.shape[0] and fmap2.shape[1] == fmap1.shape[1], op, ": fmap2 ", tuple(fmap2.shape),
+           " must have the batch and channel counts of fmap1 ", tuple(fmap1.shape))
+    refuse(coords.shape[0] == fmap1.shape[0] and coords.shape[1] == 2 and coords.shape[2] == fmap1.shape[2] and coords.shape[3] == fmap1.shape[3],
+           op, ": coords has shape ", tuple(coords.shape), ", expected [", fmap1.shape[0], ", 2, ", fmap1.shape[2], ", ", fmap1.shape[3], "]")
+    refuse(0 <= radius <= MAX_RADIUS, op, ": radius ", radius, " outside 0 .. ", MAX_RADIUS)
+
+
+def _forward_fake(fmap1, fmap2, coords, radius, scale):
+    _fake_inputs(fmap1, fmap2, coords, radius, "fn2::corr_lookup")
+    return fmap1.new_empty((fmap1.shape[0], (2 * radius + 1) ** 2, fmap1.shape[2], fmap1.shape[3]))
+
+
+def _backward_fake(fmap1, fmap2, coords, grad_output, radius, scale):
+    _fake_inputs(fmap1, fmap2, coords, radius, "fn2::corr_lookup_backward")
+    return fmap1.new_empty(fmap1.shape), fmap2.new_empty(fmap2.shape)
+
+
+def _no_coords_gradient(wanted):
+    # a silent None for coords would train wrongly: RAFT detaches coords in every iteration, and so must the caller
+    if wanted:
+        raise RuntimeError("CorrLookup: coords requires grad, but this layer has no gradient for coords (as RAFT's alt_cuda_corr): "
+                           "pass coords.detach()")
+
+
+def _setup(ctx, inputs, output):
+    _no_coords_gradient(ctx.needs_input_grad[2])
+    ctx.save_for_backward(*inputs[:3])
+    ctx.lookup_params = tuple(inputs[3:])
+
+
+def _grad(ctx, grad_output):
+    fmap1, fmap2, coords = ctx.saved_tensors
+    grad_fmap1, grad_fmap2 = _backward_op(fmap1, fmap2, coords, grad_output, *ctx.lookup_params)
+    return grad_fmap1, grad_fmap2, None, None, None
+
+
+_forward_op = fn2_ops.define("corr_lookup", "(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, float scale) -> Tensor",
+                             corr_lookup_cuda.forward_alloc, _forward_fake, _grad, _setup)
+# (backward_alloc raises or warns under torch.use_deterministic_algorithms when the operator runs, as in eager)
+_backward_op = fn2_ops.define("corr_lookup_backward",
+                              "(Tensor fmap1, Tensor fmap2, Tensor coords, Tensor grad_output, int radius, float scale) -> (Tensor, Tensor)",
+                              corr_lookup_cuda.backward_alloc, _backward_fake)
 
 
 class CorrLookupFunction(Function):
     """``apply`` goes straight to the autograd node the extension implements in C++ (``corr_lookup_cuda.apply``); ``forward`` /
-    ``backward`` are the same two calls for code that drives a Function's static methods itself."""
+    ``backward`` are the same two calls for code that drives a Function's static methods itself -- through the ``fn2`` operators
+    while ``torch.compile`` traces, which is how it sees ``apply``."""
 
     @classmethod
     def apply(cls, fmap1, fmap2, coords, radius, scale):
@@ -31,13 +87,19 @@ class CorrLookupFunction(Function):
     def forward(ctx, fmap1, fmap2, coords, radius, scale):
         ctx.save_for_backward(fmap1, fmap2, coords)
         ctx.lookup_params = (radius, scale)
+        if torch.compiler.is_compiling():
+            _no_coords_gradient(ctx.needs_input_grad[2])
+            return _forward_op(fmap1, fmap2, coords, radius, scale)
         return corr_lookup_cuda.forward_alloc(fmap1, fmap2, coords, radius, scale)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
         fmap1, fmap2, coords = ctx.saved_tensors
-        grad_fmap1, grad_fmap2 = corr_lookup_cuda.backward_alloc(fmap1, fmap2, coords, grad_output, *ctx.lookup_params)
+        if torch.compiler.is_compiling():
+            grad_fmap1, grad_fmap2 = _backward_op(fmap1, fmap2, coords, grad_output, *ctx.lookup_params)
+        else:
+            grad_fmap1, grad_fmap2 = corr_lookup_cuda.backward_alloc(fmap1, fmap2, coords, grad_output, *ctx.lookup_params)
         return grad_fmap1, grad_fmap2, None, None, None
 
 

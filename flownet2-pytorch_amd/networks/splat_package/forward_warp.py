@@ -18,6 +18,64 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import forward_warp_cuda  # built by flownet2-pytorch_amd/build.py; no fallback on purpose
+import fn2_ops
+from fn2_ops import refuse
+
+
+# ---- the fn2 operators (fn2_ops.py): the same binding calls as the static methods below, for torch.compile
+def _fake_inputs(input, flow, op):
+    """check_inputs of csrc/binding/forward_warp_cuda.cpp, as far as shapes and dtypes decide it."""
+    refuse(input.dim() == 4 and flow.dim() == 4, op, ": input and flow must be 4-D (N, C, H, W); add the missing dimensions with [None]")
+    refuse(input.shape[1] >= 1, op, ": input has no channels")
+    refuse(flow.shape[1] == 2, op, ": flow has ", flow.shape[1], " channels, expected 2 (x, y)")
+    refuse(flow.shape[0] == input.shape[0] and flow.shape[2] == input.shape[2] and flow.shape[3] == input.shape[3], op, ": flow ",
+           tuple(flow.shape), " must have the batch size, height and width of input ", tuple(input.shape),
+           " (the output has the input's size; resize the flow first)")
+    for name, t in (("input", input), ("flow", flow)):
+        refuse(t.dtype not in (torch.float16, torch.bfloat16), op, ": ", name, " must be float32, got ", t.dtype,
+               ": call .float() on it (a 16-bit accumulating output would round at every add)")
+        refuse(t.dtype == torch.float32, op, ": ", name, " must be float32, got ", t.dtype, ": convert it with .float()")
+
+
+def _forward(input, flow):
+    # (forward_alloc reads torch.are_deterministic_algorithms_enabled() when the operator runs: fixed-point sums under compile too)
+    return forward_warp_cuda.forward_alloc(input, flow)
+
+
+def _forward_fake(input, flow):
+    _fake_inputs(input, flow, "fn2::forward_warp")
+    return input.new_empty(input.shape)
+
+
+def _backward(input, flow, grad_output, want_input, want_flow):
+    grad_input, grad_flow = forward_warp_cuda.backward_alloc(input, flow, grad_output, want_input, want_flow)
+    return (grad_input if want_input else input.new_empty(0)), (grad_flow if want_flow else input.new_empty(0))
+
+
+def _backward_fake(input, flow, grad_output, want_input, want_flow):
+    _fake_inputs(input, flow, "fn2::forward_warp_backward")
+    refuse(want_input or want_flow, "fn2::forward_warp_backward: neither gradient is wanted")
+    return (input.new_empty(input.shape) if want_input else input.new_empty(0)), (flow.new_empty(flow.shape) if want_flow else input.new_empty(0))
+
+
+def _setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _grad(ctx, grad_output):
+    input, flow = ctx.saved_tensors
+    want_input, want_flow = ctx.needs_input_grad[:2]
+    if not (want_input or want_flow):
+        return None, None
+    grad_input, grad_flow = _backward_op(input, flow, grad_output, want_input, want_flow)
+    return (grad_input if want_input else None), (grad_flow if want_flow else None)
+
+
+_forward_op = fn2_ops.define("forward_warp", "(Tensor input, Tensor flow) -> Tensor", _forward, _forward_fake, _grad, _setup)
+# a gradient that is not wanted comes back with numel 0 (a schema has no optional result) and is not computed
+_backward_op = fn2_ops.define("forward_warp_backward",
+                              "(Tensor input, Tensor flow, Tensor grad_output, bool want_input, bool want_flow) -> (Tensor, Tensor)",
+                              _backward, _backward_fake)
 
 
 class ForwardWarpFunction(Function):
@@ -31,6 +89,8 @@ class ForwardWarpFunction(Function):
     @staticmethod
     def forward(ctx, input, flow):
         ctx.save_for_backward(input, flow)
+        if torch.compiler.is_compiling():   # Dynamo traces apply() through this method: the operator it can see
+            return _forward_op(input, flow)
         return forward_warp_cuda.forward_alloc(input, flow)
 
     @staticmethod
@@ -40,6 +100,9 @@ class ForwardWarpFunction(Function):
         want_input, want_flow = ctx.needs_input_grad[:2]
         if not (want_input or want_flow):
             return None, None
+        if torch.compiler.is_compiling():
+            grad_input, grad_flow = _backward_op(input, flow, grad_output, want_input, want_flow)
+            return (grad_input if want_input else None), (grad_flow if want_flow else None)
         return tuple(forward_warp_cuda.backward_alloc(input, flow, grad_output, want_input, want_flow))
 
 
