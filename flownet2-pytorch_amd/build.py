@@ -1,7 +1,8 @@
 """Builds the HIP libraries and the pybind modules of this package, in-tree, without hipify.  LIBRARIES below is the one
 description of what there is: per library its sources, its public header under include/, its version script and the pybind
-modules that link it.  libflownet2_hip.so (hand-written gfx950 kernels + C ABI) is the drop-in boundary; every other library is
-a sibling of its own, self-contained, and none links another.
+modules that link it; PREVIEW is a second table of the same descriptor for libraries that are not released yet.
+libflownet2_hip.so (hand-written gfx950 kernels + C ABI) is the drop-in boundary; every other library is a sibling of its own,
+self-contained, and none links another.
 
   python flownet2-pytorch_amd/build.py            # everything
   python flownet2-pytorch_amd/build.py --lib      # kernels + C ABI only (seconds)
@@ -32,9 +33,9 @@ MAX_JOBS = 16
 Library = collections.namedtuple("Library", "name link srcs header vmap modules")
 
 
-def _library(name, srcs, modules):
+def _library(name, srcs, modules, header_dir=""):
     suffix = "_" + name if name else ""
-    return Library(name, "flownet2_hip" + suffix, srcs, "flownet2_hip%s.h" % suffix, "exports%s.map" % suffix, modules)
+    return Library(name, "flownet2_hip" + suffix, srcs, header_dir + "flownet2_hip%s.h" % suffix, "exports%s.map" % suffix, modules)
 
 
 LIBRARIES = {lib.name: lib for lib in (
@@ -51,6 +52,19 @@ LIBRARIES = {lib.name: lib for lib in (
     _library("smooth", ["capi_smooth.hip", "smooth.hip"], ["smoothness_cuda"]),
 )}
 MODULES = [m for lib in LIBRARIES.values() for m in lib.modules]
+
+# The preview stage: libraries built by the same code with the same flags and conventions, but not yet part of the released
+# record above -- their headers live under include/preview/, their ABI version is 0 and may change until they move up into
+# LIBRARIES.  Names here and in LIBRARIES are distinct.
+PREVIEW = {lib.name: lib for lib in (
+    _library("sample", ["capi_sample.hip", "corr_sample.hip"], ["corr_sample_cuda"], header_dir="preview/"),
+)}
+assert not set(PREVIEW) & set(LIBRARIES)
+
+
+def _described(name):
+    """The descriptor of a library of either table."""
+    return LIBRARIES[name] if name in LIBRARIES else PREVIEW[name]
 
 
 def _newer(target, deps):
@@ -71,9 +85,9 @@ def _run(cmd):
 def build_lib(force=False, debug=False, ext=False):
     """libflownet2_hip.so (the product: public C ABI only) or, with debug=True, libflownet2_hip_debug.so: the same kernels plus
     the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs);
-    with ext=NAME the sibling library libflownet2_hip_NAME.so (LIBRARIES[NAME], the same flags, its own version script);
-    ext=True means "ext"."""
-    desc = LIBRARIES["ext" if ext is True else ext or ""]
+    with ext=NAME the sibling library libflownet2_hip_NAME.so (LIBRARIES[NAME] or PREVIEW[NAME], the same flags, its own version
+    script); ext=True means "ext"."""
+    desc = _described("ext" if ext is True else ext or "")
     twin = debug and not desc.name
     objdir = os.path.join(LIBDIR, "debug" if twin else desc.name) if twin or desc.name else LIBDIR
     lib = os.path.join(LIBDIR, "lib%s.so" % (desc.link + "_debug" if twin else desc.link))
@@ -106,7 +120,7 @@ def build_modules(force=False):
     shared = [os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(CSRC, "binding", "binding_status.h"),
               os.path.join(INCLUDE, "flownet2_hip.h")]   # (the sibling headers take their codes and dtype enums from flownet2_hip.h)
     outs, jobs = [], []
-    for lib, m in ((lib, m) for lib in LIBRARIES.values() for m in lib.modules):
+    for lib, m in ((lib, m) for table in (LIBRARIES, PREVIEW) for lib in table.values() for m in lib.modules):
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
         if force or not _newer(out, [src] + shared + [os.path.join(INCLUDE, lib.header)]):
@@ -137,7 +151,7 @@ def main():
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=8) as pool:
-        futs = [pool.submit(build_lib, a.force, ext=name) for name in LIBRARIES]
+        futs = [pool.submit(build_lib, a.force, ext=name) for name in list(LIBRARIES) + list(PREVIEW)]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))
         for f in futs:

@@ -29,6 +29,10 @@ constexpr StatusText STATUS_CENSUS = {"flownet2_hip_census", "invalid shape or p
                                       "unsupported size (a plane of 2^31 elements or more, or too many planes)"};
 constexpr StatusText STATUS_SMOOTH = {"flownet2_hip_smooth", "invalid shape or parameter", nullptr, "pointer not aligned to its element size",
                                       "unsupported size (a plane of 2^31 elements or more, or too many planes)"};
+// preview (include/preview/flownet2_hip_sample.h)
+constexpr StatusText STATUS_SAMPLE = {"flownet2_hip_sample", "invalid shape or parameter (1 .. 8 levels, radius 0 .. 8)", nullptr,
+                                      "pointer not aligned to its element size",
+                                      "unsupported size (2^31 query pixels or more, a slice of 2^31 cells or more, or a level beyond 2^48 cells)"};
 
 // "<op>: HIP call failed: <tag>: <text> (code <rc>)" for rc != FN2_OK.  Failure path only: callers test rc first.
 inline std::string status_message(const StatusText &lib, const char *op, int rc)

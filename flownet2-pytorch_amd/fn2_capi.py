@@ -69,6 +69,11 @@ SMOOTH_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_smooth.so")
 SMOOTH_EXPORTS = ["fn2m_abi_version", "fn2m_smoothness_forward", "fn2m_smoothness_backward"]
 FN2M_EDGE = {"exponential": 0, "gaussian": 1}
 
+# preview -- libflownet2_hip_sample.so (include/preview/flownet2_hip_sample.h): CorrSample, the lookup of a prebuilt correlation
+# pyramid (RAFT's CorrBlock); ABI version 0, may change until released
+SAMPLE_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_sample.so")
+SAMPLE_EXPORTS = ["fn2p_abi_version", "fn2p_corr_sample_forward", "fn2p_corr_sample_backward"]
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
 _RESTYPES = {"fn2_strerror": ctypes.c_char_p, "fn2_debug_set_buffer": None}   # every other entry point returns int or size_t
 # name -> (the global that holds the path (scripts point it at another build before the first call), exports, the names that
@@ -89,6 +94,9 @@ _LIBS = {
     "smooth": ("SMOOTH_LIB_PATH", SMOOTH_EXPORTS, (),
                {"fn2m_smoothness_forward": [_PTR] * 3 + [_INT] * 7 + [ctypes.c_float, ctypes.c_float, _PTR],
                 "fn2m_smoothness_backward": [_PTR] * 4 + [_INT] * 7 + [ctypes.c_float, ctypes.c_float, _PTR]}),
+    "sample": ("SAMPLE_LIB_PATH", SAMPLE_EXPORTS, (),
+               {"fn2p_corr_sample_forward": [_PTR] * 3 + [_INT] + [_PTR] * 2 + [_INT] * 4 + [_PTR],
+                "fn2p_corr_sample_backward": [_PTR] * 2 + [_INT] + [_PTR] * 3 + [_INT] * 4 + [_PTR]}),
 }
 _loaded = {}
 
@@ -153,6 +161,11 @@ def census_lib():
 def smooth_lib():
     """libflownet2_hip_smooth.so: the edge-aware smoothness term (csrc/smooth.hip)."""
     return _load("smooth")
+
+
+def sample_lib():
+    """libflownet2_hip_sample.so (preview): CorrSample (csrc/corr_sample.hip)."""
+    return _load("sample")
 
 
 def check(rc, what):
@@ -263,6 +276,40 @@ def corr_lookup_backward(fmap1, fmap2, coords, gout, radius, scale, algo=FN2L_LO
                                                      H, W, H2, W2, radius, ctypes.c_float(scale), algo, _stream(fmap1)),
               "fn2l_corr_lookup_backward")
     return g1, g2
+
+
+def _sample_geometry(levels, coords):
+    """(the host arrays H2, W2 and the pointer array of ``levels``, B, H, W): levels are (B H W) x [1 x] H2_l x W2_l, contiguous."""
+    B, _, H, W = coords.shape
+    L = len(levels)
+    assert coords.is_contiguous() and all(t.is_contiguous() and t.shape[0] == B * H * W for t in levels)
+    H2, W2 = (ctypes.c_int * L)(*[t.shape[-2] for t in levels]), (ctypes.c_int * L)(*[t.shape[-1] for t in levels])
+    return H2, W2, (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels]), B, H, W
+
+
+def corr_sample_forward(levels, coords, radius, out=None):
+    """fn2p_corr_sample_forward on contiguous device tensors; ``out``: a preallocated B x (L (2 radius + 1)^2) x H x W result."""
+    import torch
+    H2, W2, ptrs, B, H, W = _sample_geometry(levels, coords)
+    if out is None:
+        out = torch.empty((B, len(levels) * (2 * radius + 1) ** 2, H, W), dtype=coords.dtype, device=coords.device)
+    with torch.cuda.device_of(coords):
+        check(sample_lib().fn2p_corr_sample_forward(ptrs, H2, W2, len(levels), _p(coords), _p(out), B, H, W, radius, _stream(coords)),
+              "fn2p_corr_sample_forward")
+    return out
+
+
+def corr_sample_backward(levels, coords, gout, radius, out=None):
+    """fn2p_corr_sample_backward: the gradients of ``levels`` (which give the shapes only); ``out``: the preallocated gradients
+    (no pre-zeroing needed: every element is written)."""
+    import torch
+    grads = list(out) if out is not None else [torch.empty_like(t) for t in levels]
+    H2, W2, ptrs, B, H, W = _sample_geometry(grads, coords)
+    assert gout.is_contiguous() and [g.shape for g in grads] == [t.shape for t in levels]
+    with torch.cuda.device_of(coords):
+        check(sample_lib().fn2p_corr_sample_backward(H2, W2, len(grads), _p(coords), _p(gout), ptrs, B, H, W, radius, _stream(coords)),
+              "fn2p_corr_sample_backward")
+    return grads
 
 
 def _upsample_factor(flow, mask, factor):

@@ -29,6 +29,7 @@ import torch
 
 NAMESPACE = "fn2"
 _LIBS = {}   # operator name -> the library fragment its registrations hang on; lives as long as the process
+_PREVIEW = set()   # qualified names of the operators of preview layers: outside the released record that ``names()`` lists
 
 
 def refuse(cond, *message):
@@ -44,10 +45,13 @@ def _not_twice(name):
     return backward
 
 
-def define(name, schema, impl, fake, backward=None, setup_context=None):
+def define(name, schema, impl, fake, backward=None, setup_context=None, preview=False):
     """Register ``fn2::<name><schema>`` and return the operator.  ``backward`` / ``setup_context`` as ``torch.library.register_autograd``
-    takes them; without ``backward`` (the backward operators) differentiating the operator raises."""
+    takes them; without ``backward`` (the backward operators) differentiating the operator raises.  ``preview``: the operator of a
+    preview layer (build.PREVIEW): registered like any other, listed by ``names(preview=True)`` only."""
     qualname = f"{NAMESPACE}::{name}"
+    if preview:
+        _PREVIEW.add(qualname)
     if name in _LIBS:   # the wrapper's module is executed a second time (importlib.reload, a deleted sys.modules entry): replace
         # (private API; without it a second execution raises "already defined" -- tests/test_harness_pin.py re-imports the package)
         _LIBS.pop(name)._destroy()
@@ -59,7 +63,9 @@ def define(name, schema, impl, fake, backward=None, setup_context=None):
     return getattr(getattr(torch.ops, NAMESPACE), name)
 
 
-def names():
-    """The operators registered so far, sorted: ``['fn2::correlation', ...]``.  For the tests (private API, see the module docstring)."""
+def names(preview=False):
+    """The operators of the released layers registered so far, sorted: ``['fn2::correlation', ...]``; with ``preview=True`` those of
+    the preview layers instead.  For the tests (private API, see the module docstring)."""
     prefix = NAMESPACE + "::"
-    return sorted(n for n in torch._C._dispatch_get_all_op_names() if n.startswith(prefix) and "." not in n[len(prefix):])
+    return sorted(n for n in torch._C._dispatch_get_all_op_names()
+                  if n.startswith(prefix) and "." not in n[len(prefix):] and (n in _PREVIEW) == preview)

@@ -1,8 +1,10 @@
-"""``Correlation1d`` / ``Correlation1dFunction`` and ``CorrLookup`` / ``CorrLookupFunction`` / ``AlternateCorrBlock`` are exported
-here, loaded on first use: importing the 2-D layer (``networks.correlation_package.correlation``) loads neither the
-``correlation1d_cuda`` nor the ``corr_lookup_cuda`` extension."""
+"""``Correlation1d`` / ``Correlation1dFunction``, ``CorrLookup`` / ``CorrLookupFunction`` / ``AlternateCorrBlock`` and (preview)
+``CorrBlock`` / ``CorrSample`` / ``corr_sample`` are exported here, loaded on first use: importing the 2-D layer
+(``networks.correlation_package.correlation``) loads none of the ``correlation1d_cuda``, ``corr_lookup_cuda`` and
+``corr_sample_cuda`` extensions, and each of the others loads only its own."""
 _HOME = {"Correlation1d": "correlation1d", "Correlation1dFunction": "correlation1d",
-         "CorrLookup": "corr_lookup", "CorrLookupFunction": "corr_lookup", "AlternateCorrBlock": "corr_lookup"}
+         "CorrLookup": "corr_lookup", "CorrLookupFunction": "corr_lookup", "AlternateCorrBlock": "corr_lookup",
+         "CorrBlock": "corr_block", "CorrSample": "corr_block", "corr_sample": "corr_block"}
 __all__ = list(_HOME)
 
 
