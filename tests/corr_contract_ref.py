@@ -287,7 +287,8 @@ def _fill_mantissa(x, rng):
 def family_inputs(family, shape, seed):
     """in1, in2 (CPU float32) of input family 1..10:
       1-5 lowp_ref.family_inputs with fp32 ranges: 2 per-channel 2^+-20, 5 row ramp 2^+-12;
-      6 batch items at 2^+30, 2^-30, 1, 2^+30, ... (operands of each item; B >= 9 crosses the persistent workgroups' items);
+      6 batch items at 2^+30, 2^-30, 1, 2^+30, ... (operands of each item; B >= 9 crosses the forward's persistent workgroups' items -- the
+        backward's workgroups run a second task only past 256 tasks: test_gpu_f32_contract.BWD_MULTI);
       7 a ramp along the columns over 2^+-12 (the wide kernels' 32-pixel windows each see another magnitude);
       8 item 0 at 2^-66 (outputs in the fp32 subnormal range), the others at 2^+30 (outputs near 2^+60);
       9 normal data with scattered operands 65520, 1e6, -3e5, 2^20, ... (at or above 2^17 m for m <= 1/2: h overflows the f16,
@@ -350,7 +351,16 @@ def family_inputs(family, shape, seed):
 
 def grad_output(kind, shape, seed):
     """gradOutput (CPU float32): lowp_ref's 'normal', 'leaky', 'window'; 'planes' -- some displacement planes x 1e5; 'train' --
-    the ~1e-7 scale of a training gradient.  Full 24-bit mantissas."""
+    the ~1e-7 scale of a training gradient; 'items' -- normal data, item n times (2^-40, 2^20, 1)[(n + 1) % 3]: offset against
+    family 6's cycle (2^30, 2^-30, 1)[n % 3], so that along a batch the X and the G exponents of a backward task do not move
+    together, and a persistent workgroup's next task (another item) has other scale exponents for both operands.  For B = 1 the
+    rows [0, H/2) are times 2^-40 and the rows [H/2, H) times 2^20: the tasks of one item then differ by their row group.
+    m_bwd_g takes its maximum per item and row band (the rows one task's G sample can read), so the bound's derivation is
+    unchanged by this kind.  (B = 1: a grad_in2 task whose sample lies in the small rows reads gradOutput up to 10 lattice rows
+    away, in the large ones; under its scale those values overflow the f16, the sums are not finite and the elements are
+    recomputed by the fp32 chain (exact_grad), whose n U23 abs_ref + U23 |ref| lies inside delta_f16x2_bwd's 3 n U23 abs_ref
+    + U23 |ref| -- these gradients are far above the fp32 subnormal range.  The other way round, small values under a large
+    scale vanish within the 2^-24 m floor.)  Full 24-bit mantissas."""
     import numpy as np
     rng = np.random.default_rng(seed + 7)
     if kind in ("normal", "leaky", "window"):
@@ -359,6 +369,13 @@ def grad_output(kind, shape, seed):
         g = rng.standard_normal(shape)
         if kind == "planes":
             g[:, rng.choice(shape[1], 5, replace=False)] *= 1e5
+        elif kind == "items":
+            B, H = shape[0], shape[2]
+            if B == 1:
+                g[:, :, :H // 2] *= 2.0 ** -40
+                g[:, :, H // 2:] *= 2.0 ** 20
+            else:
+                g *= np.array([2.0 ** -40, 2.0 ** 20, 1.0])[(np.arange(B) + 1) % 3][:, None, None, None]
         else:
             assert kind == "train", kind
             g = g * 1e-7

@@ -4,6 +4,7 @@ rows) meets the NU = 6 blocks u of 4 neighbour lattice rows 4rg - 10 + 4u .. +3;
 source, and the per-workgroup step counts of the persistent kernel are modelled from its task order (csrc/correlation_f16x2_bwd.hip:
 channel group fastest, then row group, gradient, y parity, batch item; workgroup w runs tasks xcd_remap(w), + 256, ...)."""
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "flownet2-pytorch_amd", "csrc")
@@ -42,6 +43,61 @@ def steps_per_workgroup(B, C, H, W, max_grid=256):
             n += hi - lo + 1
         out.append(n)
     return out, ntasks
+
+
+MAX_GRID = 256
+BWD_FILES = ("correlation_f16x2_bwd.hip", "correlation_f16x2_bwd_wide.hip", "correlation_f16_bwd.hip")
+
+
+def wpx_bwd_wide():
+    """WPX of the column-window backward, read out of its source."""
+    m = re.search(r"^constexpr int WPX = (\d+);", src("correlation_f16x2_bwd_wide.hip"), re.M)
+    return int(m.group(1))
+
+
+def bwd_ntasks(B, C, H, nxw=1):
+    """Tasks of one backward launch (both gradients): 2 B 2 NRG (C / 64), times the centre windows of the wide kernel."""
+    return 2 * B * 2 * ((H // 2 + 3) // 4) * nxw * (C // 64)
+
+
+def _pairs(ntasks, decode, max_grid=MAX_GRID):
+    grid = min(ntasks, max_grid)
+    out = []
+    for w in range(grid):
+        ts = list(range(xcd_remap(w, grid), ntasks, grid))
+        out.append([(decode(t0), decode(t1)) for t0, t1 in zip(ts, ts[1:])])
+    return out
+
+
+def handovers(B, C, H, W, flip_outer=False):
+    """For each workgroup of corr_bwd_f16x2 the (task, next task) pairs it runs, each task decoded to (cg, rg, gradient, py, n)
+    in get_task's order: channel group fastest, then row group, gradient, y parity, batch item.  A workgroup with one task has
+    no pair.  flip_outer: the order of correlation_f16_bwd.hip (half / bfloat16): ..., row group, y parity, item, gradient."""
+    NRG, NCGR = (H // 2 + 3) // 4, C // 64
+
+    def decode(t):
+        cg, t = t % NCGR, t // NCGR
+        rg, t = t % NRG, t // NRG
+        if flip_outer:
+            py, t = t & 1, t >> 1
+            return cg, rg, t // B, py, t % B
+        flip, t = t % 2, t >> 1
+        return cg, rg, flip, t & 1, t >> 1
+    return _pairs(bwd_ntasks(B, C, H), decode)
+
+
+def handovers_wide(B, C, H, W):
+    """The same for corr_bwd_f16x2_wide, tasks decoded to (cg, rg, gradient, py, n, xw): NXW = ceil(W / WPX) centre windows, in
+    that kernel's get_task order -- channel group fastest, then window, row group, y parity, item, gradient."""
+    NRG, NCGR, NXW = (H // 2 + 3) // 4, C // 64, -(-W // wpx_bwd_wide())
+
+    def decode(t):
+        cg, t = t % NCGR, t // NCGR
+        xw, t = t % NXW, t // NXW
+        rg, t = t % NRG, t // NRG
+        py, t = t & 1, t >> 1
+        return cg, rg, t // B, py, t % B, xw
+    return _pairs(bwd_ntasks(B, C, H, nxw=NXW), decode)
 
 
 def test_range_is_the_blocks_that_meet_the_image():

@@ -9,6 +9,9 @@ import torch
 
 import corr_contract_ref as R
 import lowp_ref as L
+import test_bwd_u_range_host as S           # the schedule helpers
+import test_gpu_corr_task_handover as T     # the shapes of the GPU cases (the modules import no GPU code)
+import test_gpu_f32_contract as G
 from test_split_model import split
 
 CORR = L.CORR
@@ -185,3 +188,129 @@ def test_bound_rejects_wrong_kernels(mutation, family, shape, old_check):
     assert not inside
     if mutation in ("other_item", "flush_l"):
         assert old[old_check], "the older check was expected to accept this mutation"
+
+
+# ------------------------------------------------------------------ the multi-task cases of the GPU tests have power
+# Conditions on the inputs and the schedule alone (no kernel): tests/test_gpu_f32_contract.py BWD_MULTI and
+# tests/test_gpu_corr_task_handover.py mean something only if their workgroups do run several tasks and the tasks that follow
+# each other differ by what a wrong hand-over would carry over.
+NU = 6
+HANDOVERS = {(11, 192, 14, 56): (264, 8), (3, 256, 48, 64): (288, 32), (22, 64, 48, 8): (528, 272), (1, 704, 48, 8): (264, 8)}
+
+
+def _fwd_ntasks(B, H, W):
+    """Tasks of a forward launch.  W <= 64 (f16x2_common.h build_task_table): 2 NRG NU per item, real and zero-only.  W > 64
+    (correlation_f16x2_wide.hip build_pair_table): per parity and B row block b the row groups max(0, b - 5) .. min(b, NRG - 1)
+    in pairs, times the ceil(W / 32) windows."""
+    NRG = (H // 2 + 3) // 4
+    if W <= 64:
+        return B * 2 * NRG * NU
+    k = S.src("correlation_f16x2_wide.hip")
+    assert "constexpr int AW = 4;" in k and "constexpr int WPX = 8 * AW;" in k and "a.NXQ = (W + hw::WPX - 1) / hw::WPX;" in k
+    pairs = sum((min(b, NRG - 1) - max(0, b - (NU - 1)) + 2) // 2 for b in range(NRG - 1 + NU))
+    return B * 2 * pairs * -(-W // 32)
+
+
+def _multi_case(shape):
+    """(in1, in2, gradOutput) whose consecutive tasks differ: family 6 x 'items'; inside one item, the row ramp x 'items'."""
+    return G.multi_inputs(shape, 6 if shape[0] > 1 else 5, "items")
+
+
+def test_multi_task_shapes_exceed_the_grid():
+    assert set(G.BWD_MULTI) == set(HANDOVERS)
+    for shape, (ntasks, n_pairs) in HANDOVERS.items():
+        B, C, H, W = shape
+        pairs = S.handovers(*shape)
+        assert S.bwd_ntasks(B, C, H) == ntasks > S.MAX_GRID and len(pairs) == S.MAX_GRID
+        assert sum(len(p) for p in pairs) == n_pairs == ntasks - S.MAX_GRID
+    assert max(len(p) for p in S.handovers(22, 64, 48, 8)) == 2 and min(len(p) for p in S.handovers(22, 64, 48, 8)) == 1
+    # what each shape is in the table for
+    assert all(n0 == 0 and n1 == 2 for w in S.handovers(3, 256, 48, 64) for (_, _, _, _, n0), (_, _, _, _, n1) in w)
+    assert all(t0[4] == t1[4] == 0 and (t0[1], t1[1]) == (0, 5) and t0[2] != t1[2] and t0[3] != t1[3] and t0[0] != t1[0]
+               for w in S.handovers(1, 704, 48, 8) for t0, t1 in w)
+    assert all(t0[0] != t1[0] and t0[4] != t1[4] for w in S.handovers(11, 192, 14, 56) for t0, t1 in w)
+    odd = lambda rg: (S.u_range(rg, 24)[1] - S.u_range(rg, 24)[0]) % 2 == 0
+    kinds = {(odd(t0[1]), odd(t1[1])) for w in S.handovers(22, 64, 48, 8) for t0, t1 in w}
+    assert {(False, True), (True, False), (False, False)} <= kinds                  # odd and even step counts follow each other
+    # the schedule-independence cases
+    for shape, _ in T.NARROW_BWD:
+        assert S.bwd_ntasks(*shape[:3]) > S.MAX_GRID
+    for shape in T.NARROW_FWD + [T.WIDE, T.LOWP]:
+        assert _fwd_ntasks(shape[0], *shape[2:]) > S.MAX_GRID, shape
+        assert _fwd_ntasks(1, *shape[2:]) <= S.MAX_GRID, shape                         # an item alone: one task per workgroup
+    assert [_fwd_ntasks(s[0], *s[2:]) for s in T.NARROW_FWD + [T.WIDE, T.LOWP]] == [648, 288, 336, 336]
+    B, C, H, W = T.WIDE
+    nxw = -(-W // S.wpx_bwd_wide())
+    assert nxw == 2 and S.bwd_ntasks(B, C, H, nxw) == 288 and S.bwd_ntasks(1, C, H, nxw) <= S.MAX_GRID
+    assert sum(len(p) for p in S.handovers_wide(*T.WIDE)) == 32
+    assert {(t0[4], t1[4]) for w in S.handovers_wide(*T.WIDE) for t0, t1 in w} == {(0, 1)}
+    B, C, H, W = T.LOWP
+    assert S.bwd_ntasks(B, C, H) == 448 and S.bwd_ntasks(1, C, H) <= S.MAX_GRID
+    assert sum(len(p) for p in S.handovers(*T.LOWP, flip_outer=True)) == 448 - 256
+
+
+def test_single_task_shapes_have_no_handover():
+    """Why BWD_MULTI exists: on BWD_NARROW (4, 108 and 120 tasks) no workgroup of corr_bwd_f16x2 runs a second task."""
+    for shape in G.BWD_NARROW:
+        assert S.bwd_ntasks(*shape[:3]) <= S.MAX_GRID
+        assert all(p == [] for p in S.handovers(*shape)), shape
+    assert [S.bwd_ntasks(*s[:3]) for s in G.BWD_NARROW] == [4, 108, 120]
+
+
+@pytest.mark.parametrize("shape", G.BWD_MULTI, ids=lambda s: "x".join(map(str, s)))
+def test_handovers_change_the_magnitudes(shape):
+    """At least half of a shape's hand-overs change the task's G magnitude (m_bwd_g at the task's rows) by 2^16 or more, and at
+    least half change the X magnitude (m_bwd_x at the task's rows; here: of every channel of the task -- a channel keeps its
+    place in scl_sx from task to task): an exponent or sample left over from the previous task is far outside the bound."""
+    a, b, go = _multi_case(shape)
+    B, C, H, W = shape
+    mg = R.m_bwd_g(go, H, W)
+    mx = (R.m_bwd_x(b), R.m_bwd_x(a))                       # X of a grad_in1 task is in2, of a grad_in2 task in1
+    pairs = [p for w in S.handovers(*shape) for p in w]
+    far = lambda u, v: bool((torch.maximum(u / v, v / u) >= 2.0 ** 16).all())
+    g_of = lambda t: mg[t[4], 0, 8 * t[1], 0]
+    x_of = lambda t: mx[t[2]][t[4], 64 * t[0]:64 * t[0] + 64, 8 * t[1], 0]
+    ng = sum(far(g_of(t0), g_of(t1)) for t0, t1 in pairs)
+    nx = sum(far(x_of(t0), x_of(t1)) for t0, t1 in pairs)
+    print(f"{shape}: {len(pairs)} hand-overs, G magnitude changes at {ng}, X magnitude (every channel) at {nx}")
+    assert 2 * ng >= len(pairs) and 2 * nx >= len(pairs)
+
+
+@pytest.mark.parametrize("shape", G.BWD_MULTI, ids=lambda s: "x".join(map(str, s)))
+def test_a_dropped_task_is_caught(shape):
+    """An answer that leaves a task out (zeros, or whatever was there) is outside the bracket: |ref| > delta on at least 99 % of
+    the gradient elements of every item a hand-over reaches (the items of the second and third tasks; the other items cost
+    the same float64 passes again and show nothing else)."""
+    a, b, go = _multi_case(shape)
+    reached = sorted({t1[4] for w in S.handovers(*shape) for _, t1 in w})
+    if shape == (22, 64, 48, 8):
+        assert reached == list(range(10, 22))
+    for n in reached:
+        (r1, d1), (r2, d2), _ = R.bwd_deltas(a[n:n + 1], b[n:n + 1], go[n:n + 1], CORR)
+        f1, f2 = float((r1.abs() > d1).double().mean()), float((r2.abs() > d2).double().mean())
+        print(f"{shape} item {n}: |ref| > delta on {f1:.4f} (grad_input1), {f2:.4f} (grad_input2) of the elements")
+        assert f1 >= 0.99 and f2 >= 0.99
+
+
+def test_schedule_model_is_in_the_sources():
+    """handovers() / handovers_wide() restate each kernel's get_task and the launchers' grid."""
+    for name in S.BWD_FILES:
+        k = S.src(name)
+        assert "k.cg = t % p.NCGR; t /= p.NCGR;" in k and "k.rg = t % p.NRG; t /= p.NRG;" in k and "k.py = t & 1; t >>= 1;" in k, name
+        assert "const unsigned grid = ntasks < 256 ? (unsigned)ntasks : 256u;" in k, name
+        assert "xcd_remap(blockIdx.x, gridDim.x); t < ntasks; t += gridDim.x" in k, name
+    k = S.src("correlation_f16x2_bwd.hip")
+    order = ["k.cg = t % p.NCGR; t /= p.NCGR;", "k.rg = t % p.NRG; t /= p.NRG;", "#else\n        k.flip = p.nflip == 2 ? t % 2 : p.flip0;",
+             "if (p.nflip == 2) t >>= 1;", "k.py = t & 1; t >>= 1;\n        k.n = t;"]
+    at = [k.index(s) for s in order]
+    assert at == sorted(at)
+    assert "const long ntasks = 2L * B * 2 * a.NRG * a.NCGR;" in k and "a.nflip = 2; a.flip0 = 0;" in k
+    for name in S.BWD_FILES[1:]:
+        k = S.src(name)
+        assert "k.py = t & 1; t >>= 1;\n        k.n = t % p.B;\n        k.flip = t / p.B;" in k, name
+    k = S.src("correlation_f16x2_bwd_wide.hip")
+    at = [k.index(s) for s in ("k.cg = t % p.NCGR; t /= p.NCGR;", "k.xw = t % p.NXW; t /= p.NXW;", "k.rg = t % p.NRG; t /= p.NRG;")]
+    assert at == sorted(at)
+    assert "a.NXW = (W + hbw::WPX - 1) / hbw::WPX;" in k and "const long ntasks = 2L * B * 2 * a.NRG * a.NXW * a.NCGR;" in k
+    assert S.wpx_bwd_wide() == 64
+    assert "const long ntasks = 2L * B * 2 * a.NRG * a.NCGR;" in S.src("correlation_f16_bwd.hip")

@@ -163,9 +163,49 @@ def test_f16x2_backward(dev, shape):
         _bwd_case(dev, a, b, go, f"f16x2 bwd {shape} family 1, gradOutput {kind}")
 
 
-@pytest.mark.parametrize("shape", [(2, 192, 46, 56), (1, 64, 48, 72)], ids=["narrow", "wide"])
+# Workgroups that run several tasks.  corr_bwd_f16x2 is persistent: min(ntasks, 256) workgroups, ntasks = 2 B 2 NRG (C / 64), and
+# everything between two tasks of one workgroup -- the next task's operand sample and scale exponents (the other half of scl_sx,
+# scl_k[1]), the prefetch of its first X chunks and G image, the hand-over of the register sets after an odd step count -- runs
+# only past 256 tasks: BWD_NARROW above has 4, 108 and 120.  The smallest shapes that have each hand-over (counted by
+# test_bwd_u_range_host.handovers; tests/test_corr_contract_host.py checks the counts and that the inputs tell the tasks apart):
+BWD_MULTI = [
+    (11, 192, 14, 56),   # 264 tasks, 8 hand-overs: the tail; ragged last row group (HL = 7), partial width, C no power of two,
+                         # another channel group and item at the hand-over
+    (3, 256, 48, 64),    # 288 tasks, 32: the benchmark's row geometry and full width, item 0 -> item 2
+    (22, 64, 48, 8),     # 528 tasks, 272: two and three tasks per workgroup (the scl_sx half is reused), odd and even step counts
+    (1, 704, 48, 8),     # 264 tasks, 8: inside one item -- row group 0 -> 5, gradient and parity flip, another channel group
+]
+# (family, gradOutput kind): in1 / in2 that differ per channel (2), row (5), item (6, 8), and gradOutput that differs per item
+# or row band ("items"), so that consecutive tasks of a workgroup have other scale exponents
+MULTI_INPUTS = [(2, "normal"), (5, "normal"), (6, "normal"), (8, "normal"), (6, "items"), (1, "items"), (1, "train")]
+
+
+def multi_inputs(shape, fam, kind):
+    """in1, in2, gradOutput (CPU float32) of a BWD_MULTI case; family 8 keeps test_f16x2_backward's item scaling of gradOutput."""
+    B, C, H, W = shape
+    nOut, oH, oW = L.out_shape(H, W, *CORR)
+    a, b = R.family_inputs(fam, shape, seed=sum(shape))
+    go = R.grad_output(kind, (B, nOut, oH, oW), sum(shape) + fam)
+    if fam == 8:
+        go = go * torch.where(torch.arange(B) == 0, 2.0 ** -66, 2.0 ** 30).float().view(B, 1, 1, 1)
+    return a, b, go
+
+
+@pytest.mark.parametrize("fam,kind", MULTI_INPUTS, ids=lambda v: str(v))
+@pytest.mark.parametrize("shape", BWD_MULTI, ids=lambda s: "x".join(map(str, s)))
+def test_f16x2_backward_multi_task_workgroups(dev, shape, fam, kind):
+    """The per-element bound of test_f16x2_backward (bwd_deltas, every element: no family here is non-finite), AUTO == the
+    explicit selector and fully written outputs, where a workgroup runs two or three tasks whose operands have other
+    magnitudes."""
+    a, b, go = multi_inputs(shape, fam, kind)
+    assert bool(torch.isfinite(a).all() & torch.isfinite(b).all() & torch.isfinite(go).all())
+    _bwd_case(dev, a, b, go, f"f16x2 bwd multi {shape} family {fam}, gradOutput {kind}")
+
+
+@pytest.mark.parametrize("shape", [(2, 192, 46, 56), (1, 64, 48, 72), (22, 64, 48, 8)], ids=["narrow", "wide", "multi_task"])
 def test_f16x2_backward_fused(dev, shape):
-    """backward_fused against the float64 backward of the LeakyReLU-masked gradient, and bit-identical to the unfused backward."""
+    """backward_fused against the float64 backward of the LeakyReLU-masked gradient, and bit-identical to the unfused backward
+    (multi_task: 528 tasks, two and three per workgroup)."""
     import fn2_capi
     B, C, H, W = shape
     a, b = R.family_inputs(3, shape, seed=sum(shape))
