@@ -1,6 +1,7 @@
 """Builds the HIP libraries and the pybind modules of this package, in-tree, without hipify.  LIBRARIES below is the one
 description of what there is: per library its sources, its public header under include/, its version script and the pybind
-modules that link it; PREVIEW is a second table of the same descriptor for libraries that are not released yet.
+modules that link it; PREVIEW is a second table of the same descriptor for libraries that are not released yet, INCUBATING a
+third for libraries on their way into the preview.
 libflownet2_hip.so (hand-written gfx950 kernels + C ABI) is the drop-in boundary; every other library is a sibling of its own,
 self-contained, and none links another.
 
@@ -61,10 +62,22 @@ PREVIEW = {lib.name: lib for lib in (
 )}
 assert not set(PREVIEW) & set(LIBRARIES)
 
+# The incubating stage: the same descriptor and the same build once more, for libraries that are in neither record above yet (both
+# are pinned by the tests that released them).  Headers under include/preview/, ABI version 0.
+INCUBATING = {lib.name: lib for lib in (
+    _library("pyramid", ["capi_pyramid.hip", "corr_pyramid.hip"], ["corr_pyramid_cuda"], header_dir="preview/"),
+)}
+TABLES = (LIBRARIES, PREVIEW, INCUBATING)
+assert sum(len(t) for t in TABLES) == len(set().union(*TABLES)), "the three tables are disjoint"
+assert len({m for t in TABLES for lib in t.values() for m in lib.modules}) == sum(len(lib.modules) for t in TABLES for lib in t.values())
+
 
 def _described(name):
-    """The descriptor of a library of either table."""
-    return LIBRARIES[name] if name in LIBRARIES else PREVIEW[name]
+    """The descriptor of a library of any of the three tables."""
+    for table in TABLES:
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def _newer(target, deps):
@@ -85,7 +98,7 @@ def _run(cmd):
 def build_lib(force=False, debug=False, ext=False):
     """libflownet2_hip.so (the product: public C ABI only) or, with debug=True, libflownet2_hip_debug.so: the same kernels plus
     the fn2_debug_* entry points and the profiling instantiations they select (csrc/fn2_debug.h; scripts/ and ablation runs);
-    with ext=NAME the sibling library libflownet2_hip_NAME.so (LIBRARIES[NAME] or PREVIEW[NAME], the same flags, its own version
+    with ext=NAME the sibling library libflownet2_hip_NAME.so (NAME of any of the three tables, the same flags, its own version
     script); ext=True means "ext"."""
     desc = _described("ext" if ext is True else ext or "")
     twin = debug and not desc.name
@@ -120,7 +133,7 @@ def build_modules(force=False):
     shared = [os.path.join(CSRC, "binding", "binding_common.h"), os.path.join(CSRC, "binding", "binding_status.h"),
               os.path.join(INCLUDE, "flownet2_hip.h")]   # (the sibling headers take their codes and dtype enums from flownet2_hip.h)
     outs, jobs = [], []
-    for lib, m in ((lib, m) for table in (LIBRARIES, PREVIEW) for lib in table.values() for m in lib.modules):
+    for lib, m in ((lib, m) for table in TABLES for lib in table.values() for m in lib.modules):
         src = os.path.join(CSRC, "binding", m + ".cpp")
         out = os.path.join(HERE, m + ext)
         if force or not _newer(out, [src] + shared + [os.path.join(INCLUDE, lib.header)]):
@@ -151,7 +164,7 @@ def main():
     # the libraries share no object files: compile them side by side
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=8) as pool:
-        futs = [pool.submit(build_lib, a.force, ext=name) for name in list(LIBRARIES) + list(PREVIEW)]
+        futs = [pool.submit(build_lib, a.force, ext=name) for table in TABLES for name in table]
         if not a.no_debug:
             futs.append(pool.submit(build_lib, a.force, True))
         for f in futs:

@@ -33,6 +33,12 @@ constexpr StatusText STATUS_SMOOTH = {"flownet2_hip_smooth", "invalid shape or p
 constexpr StatusText STATUS_SAMPLE = {"flownet2_hip_sample", "invalid shape or parameter (1 .. 8 levels, radius 0 .. 8)", nullptr,
                                       "pointer not aligned to its element size",
                                       "unsupported size (2^31 query pixels or more, a slice of 2^31 cells or more, or a level beyond 2^48 cells)"};
+// incubating (include/preview/flownet2_hip_pyramid.h)
+constexpr StatusText STATUS_PYRAMID = {"flownet2_hip_pyramid", "invalid shape, layout or parameter (contiguous maps, 1 .. 4 levels, none of them empty)",
+                                       "dtype not supported by this op (float32 only: convert with .float())",
+                                       "pointer not aligned to its element size",
+                                       "unsupported size (2^31 query pixels or more, a slice of 2^31 cells or more, a volume beyond 2^48 cells, "
+                                       "more than 2^20 channels, or 2^31 workgroups or more)"};
 
 // "<op>: HIP call failed: <tag>: <text> (code <rc>)" for rc != FN2_OK.  Failure path only: callers test rc first.
 inline std::string status_message(const StatusText &lib, const char *op, int rc)

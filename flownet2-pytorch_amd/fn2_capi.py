@@ -74,6 +74,12 @@ FN2M_EDGE = {"exponential": 0, "gaussian": 1}
 SAMPLE_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_sample.so")
 SAMPLE_EXPORTS = ["fn2p_abi_version", "fn2p_corr_sample_forward", "fn2p_corr_sample_backward"]
 
+# incubating -- libflownet2_hip_pyramid.so (include/preview/flownet2_hip_pyramid.h): CorrPyramid, the build of that pyramid and the
+# fold of its gradients; ABI version 0, may change until released
+PYRAMID_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_pyramid.so")
+PYRAMID_EXPORTS = ["fn2y_abi_version", "fn2y_corr_pyramid_forward", "fn2y_corr_pyramid_fold"]
+FN2Y_MAX_LEVELS = 4
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
 _RESTYPES = {"fn2_strerror": ctypes.c_char_p, "fn2_debug_set_buffer": None}   # every other entry point returns int or size_t
 # name -> (the global that holds the path (scripts point it at another build before the first call), exports, the names that
@@ -97,6 +103,9 @@ _LIBS = {
     "sample": ("SAMPLE_LIB_PATH", SAMPLE_EXPORTS, (),
                {"fn2p_corr_sample_forward": [_PTR] * 3 + [_INT] + [_PTR] * 2 + [_INT] * 4 + [_PTR],
                 "fn2p_corr_sample_backward": [_PTR] * 2 + [_INT] + [_PTR] * 3 + [_INT] * 4 + [_PTR]}),
+    "pyramid": ("PYRAMID_LIB_PATH", PYRAMID_EXPORTS, (),
+                {"fn2y_corr_pyramid_forward": [_PTR] * 3 + [_INT] * 7 + [_PTR],
+                 "fn2y_corr_pyramid_fold": [_PTR, _INT, _PTR] + [_INT] * 6 + [_PTR]}),
 }
 _loaded = {}
 
@@ -166,6 +175,11 @@ def smooth_lib():
 def sample_lib():
     """libflownet2_hip_sample.so (preview): CorrSample (csrc/corr_sample.hip)."""
     return _load("sample")
+
+
+def pyramid_lib():
+    """libflownet2_hip_pyramid.so (incubating): CorrPyramid (csrc/corr_pyramid.hip)."""
+    return _load("pyramid")
 
 
 def check(rc, what):
@@ -310,6 +324,38 @@ def corr_sample_backward(levels, coords, gout, radius, out=None):
         check(sample_lib().fn2p_corr_sample_backward(H2, W2, len(grads), _p(coords), _p(gout), ptrs, B, H, W, radius, _stream(coords)),
               "fn2p_corr_sample_backward")
     return grads
+
+
+def corr_pyramid_forward(fmap1, fmap2, num_levels, out=None):
+    """fn2y_corr_pyramid_forward on contiguous float32 device tensors: the ``num_levels`` levels, (B H W) x 1 x (H2 >> l) x (W2 >> l);
+    ``out``: the preallocated levels (no initialisation needed: every element is written)."""
+    import torch
+    B, C, H, W = fmap1.shape
+    H2, W2 = fmap2.shape[2:]
+    assert fmap1.is_contiguous() and fmap2.is_contiguous() and fmap2.shape[:2] == fmap1.shape[:2]
+    levels = list(out) if out is not None else [torch.empty((B * H * W, 1, H2 >> l, W2 >> l), dtype=fmap1.dtype, device=fmap1.device)
+                                                for l in range(num_levels)]
+    assert all(t.is_contiguous() and t.numel() == B * H * W * (H2 >> l) * (W2 >> l) for l, t in enumerate(levels))
+    ptrs = (ctypes.c_void_p * num_levels)(*[t.data_ptr() for t in levels])
+    with torch.cuda.device_of(fmap1):
+        check(pyramid_lib().fn2y_corr_pyramid_forward(_p(fmap1), _p(fmap2), ptrs, num_levels, B, C, H, W, H2, W2, _stream(fmap1)),
+              "fn2y_corr_pyramid_forward")
+    return levels
+
+
+def corr_pyramid_fold(grads, shape, out=None):
+    """fn2y_corr_pyramid_fold: G, (B H W) x H2 x W2, from the levels' gradients ``grads`` (contiguous float32 device tensors; None =
+    a missing gradient, but not all of them); ``shape`` = (B, C, H, W, H2, W2); ``out``: a preallocated G (fully written)."""
+    import torch
+    B, C, H, W, H2, W2 = shape
+    first = next(g for g in grads if g is not None)
+    assert all(g is None or (g.is_contiguous() and g.numel() == B * H * W * (H2 >> l) * (W2 >> l)) for l, g in enumerate(grads))
+    if out is None:
+        out = torch.empty((B * H * W, H2, W2), dtype=first.dtype, device=first.device)
+    ptrs = (ctypes.c_void_p * len(grads))(*[None if g is None else g.data_ptr() for g in grads])
+    with torch.cuda.device_of(first):
+        check(pyramid_lib().fn2y_corr_pyramid_fold(ptrs, len(grads), _p(out), B, C, H, W, H2, W2, _stream(first)), "fn2y_corr_pyramid_fold")
+    return out
 
 
 def _upsample_factor(flow, mask, factor):

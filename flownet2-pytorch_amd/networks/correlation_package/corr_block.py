@@ -131,12 +131,18 @@ class CorrBlock:
     """The constructor and call of RAFT's ``CorrBlock`` (``core/corr.py``; ``raft.py`` with ``alternate_corr=False``): the all-pairs
     volume fmap1^T fmap2 / sqrt(C) of the ``.float()`` maps, reshaped to (B H W, 1, H, W), average-pooled once per further level;
     every call samples all levels at ``coords / 2**level`` in one kernel: B x (num_levels * (2 radius + 1)^2) x H x W float32.
-    ``coords`` is used detached, as RAFT passes it."""
+    ``coords`` is used detached, as RAFT passes it.  ``fused_build=True`` (opt-in, incubating) builds the pyramid with
+    ``corr_pyramid`` (corr_pyramid.py) instead: one fused MFMA kernel in place of the matmul, the scale and the pooling passes, the
+    same levels within the bound of include/preview/flownet2_hip_pyramid.h."""
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, fused_build=False):
         self.num_levels = num_levels
         self.radius = radius
         fmap1, fmap2 = fmap1.float(), fmap2.float()
+        if fused_build:
+            from ._fused_build import build_pyramid   # corr_pyramid.corr_pyramid; loads corr_pyramid_cuda, only where it is asked for
+            self.corr_pyramid = build_pyramid(fmap1.contiguous(), fmap2.contiguous(), num_levels)
+            return
         B, C, H, W = fmap1.shape
         H2, W2 = fmap2.shape[2:]
         corr = torch.matmul(fmap1.reshape(B, C, H * W).transpose(1, 2), fmap2.reshape(B, C, H2 * W2)) / math.sqrt(C)
