@@ -39,6 +39,12 @@ constexpr StatusText STATUS_PYRAMID = {"flownet2_hip_pyramid", "invalid shape, l
                                        "pointer not aligned to its element size",
                                        "unsupported size (2^31 query pixels or more, a slice of 2^31 cells or more, a volume beyond 2^48 cells, "
                                        "more than 2^20 channels, or 2^31 workgroups or more)"};
+// staging (include/staging/flownet2_hip_ssim.h)
+constexpr StatusText STATUS_SSIM = {"flownet2_hip_ssim",
+                                    "invalid shape or parameter (max_distance 1 .. 3, c1 and c2 finite and > 0, border reflect needs H and W above "
+                                    "max_distance)",
+                                    nullptr, "pointer not aligned to its element size",
+                                    "unsupported size (a plane of 2^31 elements or more, or too many planes)"};
 
 // "<op>: HIP call failed: <tag>: <text> (code <rc>)" for rc != FN2_OK.  Failure path only: callers test rc first.
 inline std::string status_message(const StatusText &lib, const char *op, int rc)

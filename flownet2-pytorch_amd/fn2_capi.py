@@ -80,6 +80,12 @@ PYRAMID_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_pyramid.so")
 PYRAMID_EXPORTS = ["fn2y_abi_version", "fn2y_corr_pyramid_forward", "fn2y_corr_pyramid_fold"]
 FN2Y_MAX_LEVELS = 4
 
+# staging -- libflownet2_hip_ssim.so (include/staging/flownet2_hip_ssim.h): the structural-similarity distance; ABI version 0, may
+# change until released
+SSIM_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_ssim.so")
+SSIM_EXPORTS = ["fn2i_abi_version", "fn2i_ssim_forward", "fn2i_ssim_backward"]
+FN2I_BORDER = {"zero": 0, "reflect": 1}
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
 _RESTYPES = {"fn2_strerror": ctypes.c_char_p, "fn2_debug_set_buffer": None}   # every other entry point returns int or size_t
 # name -> (the global that holds the path (scripts point it at another build before the first call), exports, the names that
@@ -106,6 +112,9 @@ _LIBS = {
     "pyramid": ("PYRAMID_LIB_PATH", PYRAMID_EXPORTS, (),
                 {"fn2y_corr_pyramid_forward": [_PTR] * 3 + [_INT] * 7 + [_PTR],
                  "fn2y_corr_pyramid_fold": [_PTR, _INT, _PTR] + [_INT] * 6 + [_PTR]}),
+    "ssim": ("SSIM_LIB_PATH", SSIM_EXPORTS, (),
+             {"fn2i_ssim_forward": [_PTR] * 3 + [_INT] * 5 + [ctypes.c_float, ctypes.c_float, _INT, _PTR],
+              "fn2i_ssim_backward": [_PTR] * 5 + [_INT] * 5 + [ctypes.c_float, ctypes.c_float, _INT, _PTR]}),
 }
 _loaded = {}
 
@@ -180,6 +189,11 @@ def sample_lib():
 def pyramid_lib():
     """libflownet2_hip_pyramid.so (incubating): CorrPyramid (csrc/corr_pyramid.hip)."""
     return _load("pyramid")
+
+
+def ssim_lib():
+    """libflownet2_hip_ssim.so (staging): the structural-similarity distance (csrc/ssim.hip)."""
+    return _load("ssim")
 
 
 def check(rc, what):
@@ -684,3 +698,30 @@ def smoothness_backward(flow, image, gout, order=1, edge_weighting="exponential"
         check(smooth_lib().fn2m_smoothness_backward(_p(flow), _p(image), _p(gout), _p(out), N, F, C, H, W, int(order), FN2M_EDGE[edge_weighting],
                                                     float(alpha), float(eps), _stream(flow)), "fn2m_smoothness_backward")
     return out
+
+
+def ssim_forward(im1, im2, max_distance=1, c1=1e-4, c2=9e-4, border="zero", out=None):
+    """fn2i_ssim_forward on contiguous float32 device tensors; ``out``: a preallocated N x C x H x W result (fully written)."""
+    import torch
+    N, C, H, W = _census_shape(im1, im2)
+    if out is None:
+        out = torch.empty_like(im1)
+    with torch.cuda.device_of(im1):
+        check(ssim_lib().fn2i_ssim_forward(_p(im1), _p(im2), _p(out), N, C, H, W, int(max_distance), float(c1), float(c2), FN2I_BORDER[border],
+                                           _stream(im1)), "fn2i_ssim_forward")
+    return out
+
+
+def ssim_backward(im1, im2, gout, max_distance=1, c1=1e-4, c2=9e-4, border="zero", want1=True, want2=True, grads=(None, None)):
+    """fn2i_ssim_backward: (grad_im1, grad_im2), None for one that is not wanted (its pointer is passed as NULL); ``grads``:
+    preallocated results."""
+    import torch
+    N, C, H, W = _census_shape(im1, im2)
+    assert gout.is_contiguous() and gout.shape == im1.shape
+    g1 = (grads[0] if grads[0] is not None else torch.empty_like(im1)) if want1 else None
+    g2 = (grads[1] if grads[1] is not None else torch.empty_like(im2)) if want2 else None
+    null = ctypes.c_void_p(0)
+    with torch.cuda.device_of(im1):
+        check(ssim_lib().fn2i_ssim_backward(_p(im1), _p(im2), _p(gout), _p(g1) if want1 else null, _p(g2) if want2 else null, N, C, H, W,
+                                            int(max_distance), float(c1), float(c2), FN2I_BORDER[border], _stream(im1)), "fn2i_ssim_backward")
+    return g1, g2

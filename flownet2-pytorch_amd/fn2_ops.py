@@ -31,6 +31,7 @@ NAMESPACE = "fn2"
 _LIBS = {}   # operator name -> the library fragment its registrations hang on; lives as long as the process
 _PREVIEW = set()   # qualified names of the operators of preview layers: outside the released record that ``names()`` lists
 _INCUBATING = set()   # ... and of incubating layers (build.INCUBATING): outside the preview record as well
+_STAGING = set()   # ... and of staging layers (build.STAGING): in none of the three listings above
 
 
 def refuse(cond, *message):
@@ -46,16 +47,18 @@ def _not_twice(name):
     return backward
 
 
-def define(name, schema, impl, fake, backward=None, setup_context=None, preview=False, incubating=False):
+def define(name, schema, impl, fake, backward=None, setup_context=None, preview=False, incubating=False, staging=False):
     """Register ``fn2::<name><schema>`` and return the operator.  ``backward`` / ``setup_context`` as ``torch.library.register_autograd``
     takes them; without ``backward`` (the backward operators) differentiating the operator raises.  ``preview``: the operator of a
     preview layer (build.PREVIEW): registered like any other, listed by ``names(preview=True)`` only; ``incubating``: the same for
-    build.INCUBATING and ``names(incubating=True)``."""
+    build.INCUBATING and ``names(incubating=True)``, ``staging`` for build.STAGING and ``names(staging=True)``."""
     qualname = f"{NAMESPACE}::{name}"
     if preview:
         _PREVIEW.add(qualname)
     if incubating:
         _INCUBATING.add(qualname)
+    if staging:
+        _STAGING.add(qualname)
     if name in _LIBS:   # the wrapper's module is executed a second time (importlib.reload, a deleted sys.modules entry): replace
         # (private API; without it a second execution raises "already defined" -- tests/test_harness_pin.py re-imports the package)
         _LIBS.pop(name)._destroy()
@@ -67,11 +70,12 @@ def define(name, schema, impl, fake, backward=None, setup_context=None, preview=
     return getattr(getattr(torch.ops, NAMESPACE), name)
 
 
-def names(preview=False, incubating=False):
+def names(preview=False, incubating=False, staging=False):
     """The operators of the released layers registered so far, sorted: ``['fn2::correlation', ...]``; with ``preview=True`` those of
-    the preview layers instead, with ``incubating=True`` those of the incubating layers.  For the tests (private API, see the module
+    the preview layers instead, with ``incubating=True`` those of the incubating layers, with ``staging=True`` those of the staging
+    layers (which none of the other three listings shows).  For the tests (private API, see the module
     docstring)."""
     prefix = NAMESPACE + "::"
     return sorted(n for n in torch._C._dispatch_get_all_op_names()
-                  if n.startswith(prefix) and "." not in n[len(prefix):] and (n in _INCUBATING) == incubating
-                  and (n in _PREVIEW) == (preview and not incubating))
+                  if n.startswith(prefix) and "." not in n[len(prefix):] and (n in _STAGING) == staging
+                  and (n in _INCUBATING) == (incubating and not staging) and (n in _PREVIEW) == (preview and not incubating and not staging))
