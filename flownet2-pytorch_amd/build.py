@@ -75,6 +75,7 @@ assert sum(len(t) for t in TABLES) == len(set().union(*TABLES)), "the three tabl
 # more line here.  Headers under include/staging/, ABI version 0.
 STAGING = {lib.name: lib for lib in (
     _library("ssim", ["capi_ssim.hip", "ssim.hip"], ["ssim_cuda"], header_dir="staging/"),
+    _library("sample1d", ["capi_sample1d.hip", "corr_sample1d.hip"], ["corr_sample1d_cuda"], header_dir="staging/"),
 )}
 ALL_TABLES = TABLES + (STAGING,)
 assert sum(len(t) for t in ALL_TABLES) == len(set().union(*ALL_TABLES)), "the tables are disjoint"

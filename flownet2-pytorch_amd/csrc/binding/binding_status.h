@@ -45,6 +45,11 @@ constexpr StatusText STATUS_SSIM = {"flownet2_hip_ssim",
                                     "max_distance)",
                                     nullptr, "pointer not aligned to its element size",
                                     "unsupported size (a plane of 2^31 elements or more, or too many planes)"};
+// staging (include/staging/flownet2_hip_sample1d.h)
+constexpr StatusText STATUS_SAMPLE1D = {"flownet2_hip_sample1d",
+                                        "invalid shape or parameter (1 .. 8 levels, radius 0 .. 8, a coords batch stride of at least H W)", nullptr,
+                                        "pointer not aligned to its element size",
+                                        "unsupported size (2^31 query pixels or more, or a level beyond 2^48 cells)"};
 
 // "<op>: HIP call failed: <tag>: <text> (code <rc>)" for rc != FN2_OK.  Failure path only: callers test rc first.
 inline std::string status_message(const StatusText &lib, const char *op, int rc)

@@ -86,6 +86,11 @@ SSIM_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_ssim.so")
 SSIM_EXPORTS = ["fn2i_abi_version", "fn2i_ssim_forward", "fn2i_ssim_backward"]
 FN2I_BORDER = {"zero": 0, "reflect": 1}
 
+# staging -- libflownet2_hip_sample1d.so (include/staging/flownet2_hip_sample1d.h): CorrSample1d, the lookup of a prebuilt 1-D
+# correlation pyramid (RAFT-Stereo's CorrBlock1D); ABI version 0, may change until released
+SAMPLE1D_LIB_PATH = os.path.join(_HERE, "lib", "libflownet2_hip_sample1d.so")
+SAMPLE1D_EXPORTS = ["fn2h_abi_version", "fn2h_corr_sample1d_forward", "fn2h_corr_sample1d_backward"]
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
 _RESTYPES = {"fn2_strerror": ctypes.c_char_p, "fn2_debug_set_buffer": None}   # every other entry point returns int or size_t
 # name -> (the global that holds the path (scripts point it at another build before the first call), exports, the names that
@@ -115,6 +120,9 @@ _LIBS = {
     "ssim": ("SSIM_LIB_PATH", SSIM_EXPORTS, (),
              {"fn2i_ssim_forward": [_PTR] * 3 + [_INT] * 5 + [ctypes.c_float, ctypes.c_float, _INT, _PTR],
               "fn2i_ssim_backward": [_PTR] * 5 + [_INT] * 5 + [ctypes.c_float, ctypes.c_float, _INT, _PTR]}),
+    "sample1d": ("SAMPLE1D_LIB_PATH", SAMPLE1D_EXPORTS, (),
+                 {"fn2h_corr_sample1d_forward": [_PTR] * 2 + [_INT, _PTR, ctypes.c_longlong, _PTR] + [_INT] * 4 + [_PTR],
+                  "fn2h_corr_sample1d_backward": [_PTR, _INT, _PTR, ctypes.c_longlong] + [_PTR] * 2 + [_INT] * 4 + [_PTR]}),
 }
 _loaded = {}
 
@@ -194,6 +202,11 @@ def pyramid_lib():
 def ssim_lib():
     """libflownet2_hip_ssim.so (staging): the structural-similarity distance (csrc/ssim.hip)."""
     return _load("ssim")
+
+
+def sample1d_lib():
+    """libflownet2_hip_sample1d.so (staging): CorrSample1d (csrc/corr_sample1d.hip)."""
+    return _load("sample1d")
 
 
 def check(rc, what):
@@ -337,6 +350,41 @@ def corr_sample_backward(levels, coords, gout, radius, out=None):
     with torch.cuda.device_of(coords):
         check(sample_lib().fn2p_corr_sample_backward(H2, W2, len(grads), _p(coords), _p(gout), ptrs, B, H, W, radius, _stream(coords)),
               "fn2p_corr_sample_backward")
+    return grads
+
+
+def _sample1d_geometry(levels, coords):
+    """(the host array W2 and the pointer array of ``levels``, coords' batch stride, B, H, W): levels are (B H W) x [1 x 1 x] W2_l,
+    contiguous; coords is B x 2 x H x W (channel 0 is read in place) or B x 1 x H x W, contiguous."""
+    B, C, H, W = coords.shape
+    L = len(levels)
+    assert coords.is_contiguous() and C in (1, 2) and all(t.is_contiguous() and t.shape[0] == B * H * W == t.numel() // t.shape[-1]
+                                                          for t in levels)
+    return (ctypes.c_int * L)(*[t.shape[-1] for t in levels]), (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels]), C * H * W, B, H, W
+
+
+def corr_sample1d_forward(levels, coords, radius, out=None):
+    """fn2h_corr_sample1d_forward on contiguous device tensors; ``out``: a preallocated B x (L (2 radius + 1)) x H x W result."""
+    import torch
+    W2, ptrs, cbs, B, H, W = _sample1d_geometry(levels, coords)
+    if out is None:
+        out = torch.empty((B, len(levels) * (2 * radius + 1), H, W), dtype=coords.dtype, device=coords.device)
+    with torch.cuda.device_of(coords):
+        check(sample1d_lib().fn2h_corr_sample1d_forward(ptrs, W2, len(levels), _p(coords), cbs, _p(out), B, H, W, radius, _stream(coords)),
+              "fn2h_corr_sample1d_forward")
+    return out
+
+
+def corr_sample1d_backward(levels, coords, gout, radius, out=None):
+    """fn2h_corr_sample1d_backward: the gradients of ``levels`` (which give the shapes only); ``out``: the preallocated gradients
+    (no pre-zeroing needed: every element is written)."""
+    import torch
+    grads = list(out) if out is not None else [torch.empty_like(t) for t in levels]
+    W2, ptrs, cbs, B, H, W = _sample1d_geometry(grads, coords)
+    assert gout.is_contiguous() and [g.shape for g in grads] == [t.shape for t in levels]
+    with torch.cuda.device_of(coords):
+        check(sample1d_lib().fn2h_corr_sample1d_backward(W2, len(grads), _p(coords), cbs, _p(gout), ptrs, B, H, W, radius, _stream(coords)),
+              "fn2h_corr_sample1d_backward")
     return grads
 
 
