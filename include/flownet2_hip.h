@@ -142,6 +142,9 @@ enum {
                                 those next to the padding stay finite, where the reference's zero-padded buffer gives
                                 0 * inf = nan.  Checked element by element in tests/test_gpu_f32_contract.py.
    Per-element bounds of the other fp32 / fp64 kernels (tests/corr_contract_ref.py; S as above, n terms per output):
+   in FN2_CORR_MFMA_BF16X3's 6 n 2^-23 S and FN2_CORR_MFMA_F16X2's 3 n 2^-23 S, n may be taken as the number of the
+   output's terms whose product is not zero (a zero factor adds exact zeros); an output without such a term is +0
+   (tests/test_gpu_split_terms.py).
      FN2_CORR_MFMA_F32      fmaf chain: n 2^-23 S + 2^-23 |exact| (the / C) + subnormal steps; subnormal products
                             are kept by v_mfma_f32_16x16x4_f32 (measured on an MI355X: operands near 2^-66);
      FN2_CORR_MFMA_BF16X3   exact 3-term split, 6 of 9 products (the dropped ones < 2^-23 |a b|): 2^-23 S + 6 n 2^-23 S

@@ -73,7 +73,9 @@ int fn2y_abi_version(void); /* FN2Y_ABI_VERSION */
  * l + 1 cell is the exact mean of four level-l cells plus three rounded adds (the multiply by 0.25 is exact above the subnormal
  * range); each add rounds a partial sum no larger than 4 pool(S0) (1 + small) by 2^-24 relative, and the sum is then divided by 4:
  * 3 2^-24 pool(S0) per step, stated as 3 U23 = FN2Y_BOUND_PER_POOL with a factor of two to spare.  The error already in the level-l
- * cells averages: pool(d_l).  The bound is this form of tests/corr_contract_ref.py delta_bf16x3 with n = C.
+ * cells averages: pool(d_l).  The bound is this form of tests/corr_contract_ref.py delta_bf16x3 with n = C.  n may be taken as
+ * the number of the element's channels whose product is not zero (a zero factor adds exact zeros): C FN2Y_BOUND_PER_CHANNEL
+ * becomes n_nz FN2Y_BOUND_PER_CHANNEL, and an element without such a channel is +0 (tests/test_gpu_split_terms.py).
  *
  * Backward.  Given the gradients g_0 .. g_{L-1} of the levels (a missing one counts as zero), the gradient of level 0 as the
  * composition would have accumulated it -- the gradient of the all-pairs volume before the scale is undone -- is the FOLD
